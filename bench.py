@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X unfolded D-ADMM forward (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs when
+--dump-outputs is given, and prints the result line (the headline with the kernel's HIP-event
+time and roofline, which come out of the timed steps themselves). --full adds the measurements
+that take runs of their own: "parity", "cpu_baseline" and "extras" (null in a plain run).
 
 Workload (BASELINE.json configs[1..3] name the single-GPU shapes; the metric is quoted on
 B=4096, P=5, n=256, K=25, m=64): one "step" = one DLASSO_unfolded.forward over a batch of 4096
@@ -15,7 +20,8 @@ rank runs its own 4096-problem batch; no collective inside the step).
 Extra fields: "roofline" (dominant kernel: fused_forward_kernel, timed with HIP events on its
 stream; FP32 MFMA roofline with SURVEY.md §8(d)'s algorithmic flop/unit P(4mn + 14n) + 2Pn deg,
 plus the HBM view with its algorithmic bytes/unit 4P(4n+m) and the PMC-measured bytes;
-"traffic" = PMC-measured HBM bytes per launch from profiles/traffic.json), "cpu_baseline" (ports of the reference forward — vectorised torch-CPU, the C
+"traffic" = PMC-measured HBM bytes per launch from profiles/traffic.json) and, with --full, "extras"
+(the secondary measurements), "cpu_baseline" (ports of the reference forward — vectorised torch-CPU, the C
 restatement and the loop-faithful eager replay — on all host threads and on 1 thread, bounded
 samples; the fastest all-thread leg is the headline), "parity" (bit-exactness vs the order-matched fp32 oracle and
 final-iterate MSE vs the fp64 restatement, on a slice of the batch; outside the timed region).
@@ -56,13 +62,23 @@ def parse():
     ap.add_argument("--m", type=int, default=64)
     ap.add_argument("--K", type=int, default=25)
     ap.add_argument("--graph-prob", type=float, default=0.5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own, after the timed steps: the parity "
+                         "check, the CPU baseline and the secondary measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float32; a "
+                         "fixed seeded sample of the iterates, which are too large to write whole)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=30.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the secondary measurements (training step, GNN model, P=16 path)")
+                    help="with --full: skip the secondary measurements (training step, GNN model, "
+                         "P=16 path)")
     ap.add_argument("--traffic-file", default=os.path.join(ROOT, "profiles", "traffic.json"),
                     help="PMC-derived HBM bytes per launch (written from a rocprofv3 --pmc pass)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def make_args(K):
@@ -190,9 +206,9 @@ def main():
 
     def step():
         with torch.no_grad():
-            Y, _ = model(bt, graph_list)
+            Y, hyp = model(bt, graph_list)
         statuses.append(model.last_status)     # device word, no host sync here
-        return Y
+        return Y, hyp
 
     # W warmup steps, then more of the same until min_warmup_s of wall time has passed (steady
     # clocks before the timed region; every rank warms up alike, the count is reported)
@@ -209,17 +225,25 @@ def main():
     # patch the library entry point only for the timed region's event bookkeeping
     L = _lib.load()
     L.dadmm_forward = timed
+    # the forward draws its inits from torch's generator: seeded here, after a warm-up whose
+    # length depends on the clock, the timed steps compute the same values in every run
+    torch.manual_seed(97531 + rank)
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(a.steps):
+    for _ in range(a.steps - 1):
         step()
+    last = step()              # what the caller receives from the last timed step
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     L.dadmm_forward = orig_forward
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs if world == 1 else os.path.join(a.dump_outputs, f"rank{rank}"),
+                     *last)
+    del last
     kern_ms = float(np.mean([e0.elapsed_time(e1) for e0, e1 in ev_pairs]))
     # every timed forward must have run the work it claims: a fired guard (status != 0) means
     # the batch went through the reference's reset / recompute path instead
@@ -264,17 +288,19 @@ def main():
             except Exception:
                 traffic = None
 
-        parity = check_parity(O, model, A, b, G, dev, P, n, m, K)
+        # what takes runs of its own is measured only with --full
+        parity = check_parity(O, model, A, b, G, dev, P, n, m, K) if a.full else None
         # the CPU baseline and the single-GPU secondary measurements belong to the N = 1 run
         cpu = None
-        if not (a.no_cpu_baseline or world > 1):
+        if a.full and not (a.no_cpu_baseline or world > 1):
             cpu = cpu_baseline(O, A, b, G, model, P, n, m, K, a.cpu_baseline_seconds)
             # BASELINE configs[0], the reference's own CPU-runnable case ("run
             # at c1 and at H"): P=5, n=200, m_p=50, batch=32, K=15
             cpu["configs0"] = cpu_baseline_configs0(O, a.cpu_baseline_seconds / 3)
         status = {"headline_forward": head_status}
-        extras = None if (a.no_extras or world > 1) else secondary(O, dev, A, b, x, G, model, P, n,
-                                                                   m, K, B, status)
+        extras = None
+        if a.full and not (a.no_extras or world > 1):
+            extras = secondary(O, dev, A, b, x, G, model, P, n, m, K, B, status)
         out = {
             "metric": "ADMM-iters/sec (node), batch=4096 P=5 n=256 K=25; final-iter MSE vs ref",
             "value": value,
@@ -282,6 +308,7 @@ def main():
             "n_gpus": world,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": a.full,
             "warmup_steps_run": warm_steps,
             "warmup_s": round(warm_s, 3),
             "ms_per_step": ms_per_step,
@@ -336,6 +363,30 @@ def _or_all(statuses) -> int:
     for w in v.cpu().tolist():
         out |= int(w)
     return out
+
+
+DUMP_MAX_ELEMS = 6_000_000     # per array: 24 MB of float32, two arrays and the table < 64 MB
+
+
+def _whole_or_sample(t, seed):
+    """``t`` as a float32 numpy array: whole when it has at most DUMP_MAX_ELEMS elements, else
+    the elements at DUMP_MAX_ELEMS flat positions drawn once from a seeded generator (sorted;
+    the same positions for the same shape in every run and build)."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() <= DUMP_MAX_ELEMS:
+        return t.detach().float().cpu().numpy()
+    idx = np.sort(np.random.default_rng(seed).integers(0, flat.numel(), size=DUMP_MAX_ELEMS))
+    return flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+
+
+def dump_outputs(dirname, Y, hyp):
+    """What ``DLASSO_unfolded.forward`` returned in the last timed step, as float32 .npy files:
+    Y.npy (the iterates [K,B,P,n,1], or a seeded sample of them), Y_final.npy (the final iterate
+    Y[-1], or a seeded sample of it) and hyp.npy (the last hyper-parameter row [H,4,1])."""
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "Y.npy"), _whole_or_sample(Y, 20240))
+    np.save(os.path.join(dirname, "Y_final.npy"), _whole_or_sample(Y[-1], 20241))
+    np.save(os.path.join(dirname, "hyp.npy"), _whole_or_sample(hyp, 20242))
 
 
 def _event_ms(fn, reps, warm=2):

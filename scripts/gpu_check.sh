@@ -20,13 +20,13 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smo
 rc=$?; echo "smoke rc=$rc" | tee -a "$OUT/status.txt"; tail -3 "$OUT/smoke.log"; stop_if_fatal $rc
 if [ "${SKIP_BENCH:-0}" = 0 ]; then
   echo "== bench" | tee -a "$OUT/status.txt"
-  timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
+  timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
   rc=$?; echo "bench rc=$rc" | tee -a "$OUT/status.txt"; tail -c 3000 "$OUT/bench.json"; tail -5 "$OUT/bench.err"; stop_if_fatal $rc
 fi
 if [ "${SKIP_PROF:-0}" = 0 ]; then
   echo "== rocprofv3 kernel trace" | tee -a "$OUT/status.txt"
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o kt -- \
-     python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/prof_bench.json" 2> "$OUT/prof.err"
+     python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline >"$OUT/prof_bench.json" 2> "$OUT/prof.err"
   rc=$?; echo "rocprof rc=$rc" | tee -a "$OUT/status.txt"; stop_if_fatal $rc
   find "$OUT/prof" -name '*stats*' | head
 fi

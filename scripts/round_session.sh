@@ -19,7 +19,7 @@ if [ -n "$TESTS" ]; then
     run tests 900 python -u -m pytest $TESTS -m gpu -q --timeout 300 --timeout-method thread -p no:cacheprovider
 fi
 if [ -n "$BENCH" ]; then
-    run bench 600 python bench.py --steps 20 --warmup 5
+    run bench 600 python bench.py --full --steps 20 --warmup 5
 fi
 if [ -n "$BENCH2" ]; then
     DADMM_DIST_BACKEND=gloo run bench2 300 python bench.py --gpus 2 --steps 5 --warmup 2 --no-extras --no-cpu-baseline

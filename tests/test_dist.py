@@ -32,15 +32,35 @@ def test_shard_range_covers_batch():
         D.shard_range(8, 2, 2)
 
 
+def _graphs(P, B):
+    import oracle as O
+    return [O.connected_er_graph(P, 0.5, seed=30 + s) for s in range(B)]
+
+
 def _problem(seed=0):
     import oracle as O
     P, m, n, B, K = 4, 12, 32, 7, 6
     A, b, x = O.make_problem(P, m, n, B, seed=seed)
-    graphs = [O.connected_er_graph(P, 0.5, seed=30 + s) for s in range(B)]
+    graphs = _graphs(P, B)
     rng = np.random.default_rng(1)
     y0, U0, d0 = (1e-2 * rng.standard_normal((3, B, P, n))).astype(np.float32)
     param = (0.3 * rng.standard_normal((K, P, 4))).astype(np.float64)
     return A, b, x, graphs, y0, U0, d0, param
+
+
+def _save_problem(path):
+    """The problem as the parent drew it, for the ranks to load: make_problem's fp32 SVD and GEMMs
+    round differently with the host's thread count (the ranks run on 1 thread, the parent on all),
+    so a rank that drew its own would not hold the parent's A and b bit for bit."""
+    A, b, x, _, y0, U0, d0, param = prob = _problem()
+    np.savez(path, A=A, b=b, x=x, y0=y0, U0=U0, d0=d0, param=param)
+    return prob
+
+
+def _load_problem(path):
+    z = np.load(path)
+    graphs = _graphs(z["A"].shape[0], len(z["b"]))      # seeded networkx graphs: no rounding
+    return z["A"], z["b"], z["x"], graphs, z["y0"], z["U0"], z["d0"], z["param"]
 
 
 def _loss_and_grad(sl, A, b, x, graphs, y0, U0, d0, param):
@@ -64,13 +84,13 @@ def _loss_and_grad(sl, A, b, x, graphs, y0, U0, d0, param):
     return loss_mean.detach(), loss_final.detach(), seq.param
 
 
-def _worker(rank, world, port, out_path):
+def _worker(rank, world, port, out_path, problem_path):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
                       WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     torch.set_num_threads(1)
     r, w, _ = D.init_from_env("gloo")
     assert (r, w) == (rank, world)
-    A, b, x, graphs, y0, U0, d0, param = _problem()
+    A, b, x, graphs, y0, U0, d0, param = _load_problem(problem_path)
     lo, hi = D.shard_range(b.shape[0], r, w)
     lm, lf, p = _loss_and_grad(slice(lo, hi), A, b, x, graphs, y0, U0, d0, param)
     gm, gf = D.global_losses(lm, lf, hi - lo)
@@ -90,10 +110,11 @@ def _free_port():
 @pytest.mark.parametrize("world", [2, 3])
 def test_sharded_loss_and_gradient_equal_full_batch(tmp_path, world):
     out = str(tmp_path / "r0.npz")
-    mp.start_processes(_worker, args=(world, _free_port(), out), nprocs=world, join=True,
+    problem = str(tmp_path / "problem.npz")
+    A, b, x, graphs, y0, U0, d0, param = _save_problem(problem)
+    mp.start_processes(_worker, args=(world, _free_port(), out, problem), nprocs=world, join=True,
                        start_method="spawn")
     got = np.load(out)
-    A, b, x, graphs, y0, U0, d0, param = _problem()
     lm, lf, p = _loss_and_grad(slice(0, b.shape[0]), A, b, x, graphs, y0, U0, d0, param)
     # compute_loss adds 1e-8 to each shard's loss; the weighted mean keeps exactly one 1e-8
     np.testing.assert_allclose(got["loss_mean"], lm.numpy(), rtol=1e-12, atol=1e-14)

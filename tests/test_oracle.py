@@ -17,7 +17,6 @@ from oracle import ref_torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = os.path.join(HERE, "golden")
-REF = "/root/reference"
 TRAINED = np.load(os.path.join(GOLD, "fixture_25_iter_general_learning_seq_hyp_param.npy"))
 MAXP = [0.1, 0.99, 0.99, 0.99]
 
@@ -266,12 +265,13 @@ def test_oracle_reproduces_goldens(path):
     np.testing.assert_allclose(Y64[g["k64"]], g["Y64"], rtol=0, atol=1e-12)
 
 
-# ---- the reference's shipped data fixtures (read as data only; absent on GPU boxes) -------------
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
+# ---- the reference's shipped data fixtures (stored as data under tests/golden/) ----------------
 def test_fixture_A_singular_values_saturate():
-    """results/25_iter_general_learning/A.pt: every sigma(A_p) == 10 (set_A's clamp,
-    gnn_dlasso_utils.py:14; m=100 < n=500 puts all singular values above 10)."""
-    A = O.load_fixture_tensor(os.path.join(REF, "results/25_iter_general_learning/A.pt"))
+    """results/25_iter_general_learning/A.pt (stored by tests/golden/make_fixtures.py): every
+    sigma(A_p) == 10 (set_A's clamp, gnn_dlasso_utils.py:14; m=100 < n=500 puts all singular
+    values above 10)."""
+    A = np.load(os.path.join(GOLD, "fixture_25_iter_general_learning_A.npy"))
+    assert A.dtype == np.float32
     A = A.reshape(5, 100, 500)
     s = np.linalg.svd(A.astype(np.float64), compute_uv=False)
     np.testing.assert_allclose(s, 10.0, rtol=1e-5)
