@@ -30,7 +30,17 @@ int ok() {
     return DADMM_OK;
 }
 
+int hip_rc(hipError_t e, const char* what) {
+    if (e != hipSuccess) return fail(DADMM_EHIP, "%s: %s", what, hipGetErrorString(e));
+    return ok();
+}
+
 bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+// every pointer 16-byte aligned (NULL passes: list optional pointers with the required ones)
+template <typename... T>
+bool all_aligned16(const T*... p) { return (... && aligned16(p)); }
+template <typename... T>
+bool any_null(const T*... p) { return (... || (p == nullptr)); }
 
 int check_dims(const dadmm_dims* d) {
     if (d == nullptr) return fail(DADMM_EINVAL, "dims is NULL");
@@ -61,6 +71,49 @@ int check_m(const dadmm_dims* d) {
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+int check_scratch256(const void* scratch) {
+    if (((uintptr_t)scratch & 255u) != 0) return fail(DADMM_EINVAL, "scratch must be 256-byte aligned");
+    return DADMM_OK;
+}
+int check_n4(const dadmm_dims* d, const char* who = "") {
+    if ((d->n & 3) != 0) return fail(DADMM_EUNSUPPORTED, "n=%d: %sneeds n %% 4 == 0 (zero-pad n)", d->n, who);
+    return DADMM_OK;
+}
+// one iterate [B][P][n] in 32-bit byte offsets (buffer descriptors)
+bool iterate_fits(const dadmm_dims* d) { return (size_t)d->B * d->P * d->n * 4 < ((size_t)1 << 31); }
+int check_iterate(const dadmm_dims* d) {
+    if (!iterate_fits(d)) return fail(DADMM_EUNSUPPORTED, "B*P*n*4 >= 2^31 bytes per iterate (split the batch)");
+    return DADMM_OK;
+}
+// the adjoints of an empty batch: dhyp = 0
+int zero_dhyp(const dadmm_dims* d, float* dhyp, void* stream) {
+    return hip_rc(hipMemsetAsync(dhyp, 0, sizeof(float) * (size_t)d->K * d->hyp_rows * 4, (hipStream_t)stream),
+                  "memset");
+}
+
+// What every kernel argument struct takes from (dims, op): the prepared operator's two halves and
+// the problem sizes. op may be NULL for the launches that read no operator.
+template <typename Args>
+void fill_args(Args& a, const dadmm_dims* d, const void* op) {
+    a.A = (const float*)op;
+    a.At = op ? a.A + (size_t)d->P * m_pad_of(d) * n_pad_of(d) : nullptr;
+    a.B = d->B;
+    a.m = d->m;
+    a.n = d->n;
+    a.K = d->K;
+    a.hyp_rows = d->hyp_rows;
+    a.variant = d->variant;
+}
+// The same for the structs of the any-shape paths, which carry P and the padded sizes at run time.
+template <typename Args>
+void fill_args_padded(Args& a, const dadmm_dims* d, const void* op) {
+    fill_args(a, d, op);
+    a.P = d->P;
+    a.m_pad = m_pad_of(d);
+    a.n_pad = n_pad_of(d);
+    a.graph_shared = d->graph_shared;
+}
+
 }  // namespace
 
 extern "C" {
@@ -84,9 +137,7 @@ int dadmm_prepare_operator(const dadmm_dims* d, const float* A, void* op, void* 
     const int np = n_pad_of(d);
     float* Apad = (float*)op;
     float* Atpad = Apad + (size_t)d->P * m_pad_of(d) * np;
-    hipError_t e = dadmm::launch_prepare(A, Apad, Atpad, d->P, d->m, d->n, np, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "prepare launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_prepare(A, Apad, Atpad, d->P, d->m, d->n, np, (hipStream_t)stream), "prepare launch");
 }
 
 }  // extern "C"
@@ -99,10 +150,8 @@ int check_fused_shape(const dadmm_dims* d, const uint32_t* nbr_order, int* graph
     if (d->m > dadmm::M_PAD)   // the fused kernels hold one m-group of R on chip
         return fail(DADMM_EUNSUPPORTED, "m=%d > %d rows per agent: not a fused shape", d->m,
                     dadmm::M_PAD);
-    if ((d->n & 3) != 0)
-        return fail(DADMM_EUNSUPPORTED, "n=%d: the fused kernel needs n %% 4 == 0 (zero-pad n)", d->n);
-    if ((size_t)d->B * d->P * d->n * 4 >= ((size_t)1 << 31))
-        return fail(DADMM_EUNSUPPORTED, "B*P*n*4 >= 2^31 bytes per iterate (split the batch)");
+    int rc = check_n4(d, "the fused kernel ");
+    if (rc || (rc = check_iterate(d)) != DADMM_OK) return rc;
     if (nbr_order != nullptr && d->graph_shared)
         return fail(DADMM_EINVAL, "nbr_order needs per-sample graphs (graph_shared = 0)");
     if (nbr_order != nullptr && d->P > 8)
@@ -113,31 +162,11 @@ int check_fused_shape(const dadmm_dims* d, const uint32_t* nbr_order, int* graph
     return DADMM_OK;
 }
 
-int forward_impl(const dadmm_dims* d, const void* op, const float* b, const uint64_t* nbr,
-                 const uint32_t* nbr_order, const float* deg, const float* hyp, const float* y0,
-                 const float* U0, const float* d0, float* Y, float* Grec, float* Urec,
-                 float* U_out, int32_t* status, void* stream, bool rec) {
-    int rc = check_dims(d);
-    if (rc) return rc;
-    if (d->B == 0 || d->K == 0) return ok();
-    if (rec && (Grec == nullptr || Urec == nullptr || !aligned16(Grec) || !aligned16(Urec)))
-        return fail(DADMM_EINVAL, "Grec and Urec must be non-NULL and 16-byte aligned");
-    if (!op || !b || !nbr || !deg || !hyp || !y0 || !U0 || !d0 || !Y)
-        return fail(DADMM_EINVAL, "a required pointer is NULL");
-    if (!aligned16(op)) return fail(DADMM_EINVAL, "op workspace must be 16-byte aligned");
-    if (!aligned16(Y) || !aligned16(y0) || !aligned16(U0) || !aligned16(d0) ||
-        (U_out != nullptr && !aligned16(U_out)))
-        return fail(DADMM_EINVAL, "Y, y0, U0, d0 and U_out must be 16-byte aligned");
-    int graph = 0, nt = 0;
-    if ((rc = check_fused_shape(d, nbr_order, &graph, &nt)) != DADMM_OK) return rc;
-    dadmm::fused_fn_ptr fn = rec ? dadmm::find_fused_rec(d->P, nt, graph) : dadmm::find_fused(d->P, nt, graph);
-    if (fn == nullptr)
-        return fail(DADMM_EUNSUPPORTED, "no fused kernel for P=%d n=%d (n_pad=%d)", d->P, d->n,
-                    64 * nt);
-    const int np = 64 * nt;
-    dadmm::FusedArgs a;
-    a.A = (const float*)op;
-    a.At = a.A + (size_t)d->P * m_pad_of(d) * np;
+// the fused forward's arguments (plain, recording and the column-split form share them)
+void fill_fused(dadmm::FusedArgs& a, const dadmm_dims* d, const void* op, const float* b, const uint64_t* nbr,
+                const uint32_t* nbr_order, const float* deg, const float* hyp, const float* y0, const float* U0,
+                const float* d0, float* Y, float* U_out, int32_t* status) {
+    fill_args(a, d, op);
     a.b = b;
     a.nbr = nbr;
     a.nbr_order = nbr_order;
@@ -149,17 +178,34 @@ int forward_impl(const dadmm_dims* d, const void* op, const float* b, const uint
     a.Y = Y;
     a.U_out = U_out;
     a.status = status;
+    a.Grec = nullptr;
+    a.Urec = nullptr;
+}
+
+int forward_impl(const dadmm_dims* d, const void* op, const float* b, const uint64_t* nbr,
+                 const uint32_t* nbr_order, const float* deg, const float* hyp, const float* y0,
+                 const float* U0, const float* d0, float* Y, float* Grec, float* Urec,
+                 float* U_out, int32_t* status, void* stream, bool rec) {
+    int rc = check_dims(d);
+    if (rc) return rc;
+    if (d->B == 0 || d->K == 0) return ok();
+    if (rec && (any_null(Grec, Urec) || !all_aligned16(Grec, Urec)))
+        return fail(DADMM_EINVAL, "Grec and Urec must be non-NULL and 16-byte aligned");
+    if (any_null(op, b, nbr, deg, hyp, y0, U0, d0, Y)) return fail(DADMM_EINVAL, "a required pointer is NULL");
+    if (!aligned16(op)) return fail(DADMM_EINVAL, "op workspace must be 16-byte aligned");
+    if (!all_aligned16(Y, y0, U0, d0, U_out))
+        return fail(DADMM_EINVAL, "Y, y0, U0, d0 and U_out must be 16-byte aligned");
+    int graph = 0, nt = 0;
+    if ((rc = check_fused_shape(d, nbr_order, &graph, &nt)) != DADMM_OK) return rc;
+    dadmm::fused_fn_ptr fn = rec ? dadmm::find_fused_rec(d->P, nt, graph) : dadmm::find_fused(d->P, nt, graph);
+    if (fn == nullptr)
+        return fail(DADMM_EUNSUPPORTED, "no fused kernel for P=%d n=%d (n_pad=%d)", d->P, d->n,
+                    64 * nt);
+    dadmm::FusedArgs a;
+    fill_fused(a, d, op, b, nbr, nbr_order, deg, hyp, y0, U0, d0, Y, U_out, status);
     a.Grec = Grec;
     a.Urec = Urec;
-    a.B = d->B;
-    a.m = d->m;
-    a.n = d->n;
-    a.K = d->K;
-    a.hyp_rows = d->hyp_rows;
-    a.variant = d->variant;
-    hipError_t e = fn(a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "fused launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(fn(a, (hipStream_t)stream), "fused launch");
 }
 
 }  // namespace
@@ -201,7 +247,7 @@ SplitPlan split_plan(const dadmm_dims* d) {
     if (d == nullptr || d->B <= 0 || d->K <= 0 || d->P < 1 || d->P > 6 || d->m < 1 ||
         d->m > dadmm::M_PAD || d->n < 1 || (d->n & 3) != 0 || d->hyp_rows < 1)
         return sp;
-    if ((size_t)d->B * d->P * d->n * 4 >= ((size_t)1 << 31)) return sp;
+    if (!iterate_fits(d)) return sp;
     const int nt = dadmm::fused_nt(d->n);
     if (nt != 2 && nt != 4) return sp;
     const int cus = device_cus();
@@ -238,10 +284,9 @@ int dadmm_forward_split(const dadmm_dims* d, const void* op, const float* b, con
     int rc = check_dims(d);
     if (rc) return rc;
     if (d->B == 0 || d->K == 0) return ok();
-    if (!op || !b || !nbr || !deg || !hyp || !y0 || !U0 || !d0 || !Y || !flags || !scratch)
+    if (any_null(op, b, nbr, deg, hyp, y0, U0, d0, Y, flags, scratch))
         return fail(DADMM_EINVAL, "a required pointer is NULL");
-    if (!aligned16(op) || !aligned16(Y) || !aligned16(y0) || !aligned16(U0) || !aligned16(d0) ||
-        !aligned16(flags) || !aligned16(scratch) || (U_out != nullptr && !aligned16(U_out)))
+    if (!all_aligned16(op, Y, y0, U0, d0, flags, scratch, U_out))
         return fail(DADMM_EINVAL, "op, Y, y0, U0, d0, U_out, flags and scratch must be 16-byte aligned");
     int graph = 0, nt = 0;
     if ((rc = check_fused_shape(d, nbr_order, &graph, &nt)) != DADMM_OK) return rc;
@@ -252,38 +297,14 @@ int dadmm_forward_split(const dadmm_dims* d, const void* op, const float* b, con
     dadmm::split_fn_ptr fn = dadmm::find_split(d->P, nt, graph);
     if (fn == nullptr)
         return fail(DADMM_EUNSUPPORTED, "no split kernel for P=%d n_pad=%d", d->P, 64 * nt);
-    const int np = 64 * nt;
     dadmm::SplitArgs sa;
-    dadmm::FusedArgs& a = sa.f;
-    a.A = (const float*)op;
-    a.At = a.A + (size_t)d->P * m_pad_of(d) * np;
-    a.b = b;
-    a.nbr = nbr;
-    a.nbr_order = nbr_order;
-    a.deg = deg;
-    a.hyp = hyp;
-    a.y0 = y0;
-    a.U0 = U0;
-    a.d0 = d0;
-    a.Y = Y;
-    a.U_out = U_out;
-    a.status = status;
-    a.Grec = nullptr;
-    a.Urec = nullptr;
-    a.B = d->B;
-    a.m = d->m;
-    a.n = d->n;
-    a.K = d->K;
-    a.hyp_rows = d->hyp_rows;
-    a.variant = d->variant;
+    fill_fused(sa.f, d, op, b, nbr, nbr_order, deg, hyp, y0, U0, d0, Y, U_out, status);
     sa.xflag = (uint32_t*)flags;
     sa.xbuf = (float*)scratch;
     sa.groups = sp.groups;
     sa.tiles = sp.tiles;
     sa.spin_ticks = 20000000ull;   // 0.2 s at the 100 MHz s_memrealtime clock
-    hipError_t e = fn(sa, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "split launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(fn(sa, (hipStream_t)stream), "split launch");
 }
 
 size_t dadmm_backward_scratch_bytes(const dadmm_dims* d) {
@@ -301,16 +322,10 @@ int dadmm_backward(const dadmm_dims* d, const void* op, const uint64_t* nbr,
     if (rc) return rc;
     if (d->K == 0) return ok();
     if (!dhyp) return fail(DADMM_EINVAL, "dhyp is NULL");
-    if (d->B == 0) {
-        hipError_t e = hipMemsetAsync(dhyp, 0, sizeof(float) * (size_t)d->K * d->hyp_rows * 4,
-                                      (hipStream_t)stream);
-        if (e != hipSuccess) return fail(DADMM_EHIP, "memset: %s", hipGetErrorString(e));
-        return ok();
-    }
-    if (!op || !nbr || !deg || !hyp || !y0 || !d0 || !Y || !Grec || !Urec || !gY || !scratch)
+    if (d->B == 0) return zero_dhyp(d, dhyp, stream);
+    if (any_null(op, nbr, deg, hyp, y0, d0, Y, Grec, Urec, gY, scratch))
         return fail(DADMM_EINVAL, "a required pointer is NULL");
-    if (!aligned16(op) || !aligned16(Y) || !aligned16(y0) || !aligned16(d0) || !aligned16(Grec) ||
-        !aligned16(Urec) || !aligned16(gY) || !aligned16(scratch))
+    if (!all_aligned16(op, Y, y0, d0, Grec, Urec, gY, scratch))
         return fail(DADMM_EINVAL, "op, Y, y0, d0, Grec, Urec, gY and scratch must be 16-byte aligned");
     int graph = 0, nt = 0;
     if ((rc = check_fused_shape(d, nbr_order, &graph, &nt)) != DADMM_OK) return rc;
@@ -318,10 +333,8 @@ int dadmm_backward(const dadmm_dims* d, const void* op, const uint64_t* nbr,
     if (fn == nullptr)
         return fail(DADMM_EUNSUPPORTED, "no adjoint kernel for P=%d n=%d (n_pad=%d)", d->P, d->n,
                     64 * nt);
-    const int np = 64 * nt;
     dadmm::BackwardArgs a;
-    a.A = (const float*)op;
-    a.At = a.A + (size_t)d->P * m_pad_of(d) * np;
+    fill_args(a, d, op);
     a.nbr = nbr;
     a.nbr_order = nbr_order;
     a.deg = deg;
@@ -333,19 +346,10 @@ int dadmm_backward(const dadmm_dims* d, const void* op, const uint64_t* nbr,
     a.Urec = Urec;
     a.gY = gY;
     a.partial = (float*)scratch;
-    a.B = d->B;
-    a.m = d->m;
-    a.n = d->n;
-    a.K = d->K;
-    a.hyp_rows = d->hyp_rows;
-    a.variant = d->variant;
-    hipError_t e = fn(a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "adjoint launch: %s", hipGetErrorString(e));
+    if ((rc = hip_rc(fn(a, (hipStream_t)stream), "adjoint launch")) != DADMM_OK) return rc;
     const int nwg = (d->B + dadmm::BT - 1) / dadmm::BT;
-    e = dadmm::launch_backward_reduce(a.partial, dhyp, nwg, d->K, d->P, d->hyp_rows,
-                                      (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "adjoint reduce launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_backward_reduce(a.partial, dhyp, nwg, d->K, d->P, d->hyp_rows, (hipStream_t)stream),
+                  "adjoint reduce launch");
 }
 
 size_t dadmm_adjoint_scratch_bytes(const dadmm_dims* d) {
@@ -363,31 +367,20 @@ int dadmm_adjoint(const dadmm_dims* d, const void* op, const int32_t* visit_ptr,
     if (rc) return rc;
     if (d->K == 0) return ok();
     if (!dhyp) return fail(DADMM_EINVAL, "dhyp is NULL");
-    if (d->B == 0) {
-        hipError_t e = hipMemsetAsync(dhyp, 0, sizeof(float) * (size_t)d->K * d->hyp_rows * 4,
-                                      (hipStream_t)stream);
-        if (e != hipSuccess) return fail(DADMM_EHIP, "memset: %s", hipGetErrorString(e));
-        return ok();
-    }
-    if (!op || !visit_ptr || !visit_q || !deg || !hyp || !y0 || !d0 || !Y || !Grec || !Urec || !gY ||
-        !scratch)
+    if (d->B == 0) return zero_dhyp(d, dhyp, stream);
+    if (any_null(op, visit_ptr, visit_q, deg, hyp, y0, d0, Y, Grec, Urec, gY, scratch))
         return fail(DADMM_EINVAL, "a required pointer is NULL");
-    if (!aligned16(op) || !aligned16(Y) || !aligned16(y0) || !aligned16(d0) || !aligned16(Grec) ||
-        !aligned16(Urec) || !aligned16(gY))
+    if (!all_aligned16(op, Y, y0, d0, Grec, Urec, gY))
         return fail(DADMM_EINVAL, "op, Y, y0, d0, Grec, Urec and gY must be 16-byte aligned");
-    if (((uintptr_t)scratch & 255u) != 0) return fail(DADMM_EINVAL, "scratch must be 256-byte aligned");
-    if ((rc = check_m(d)) != DADMM_OK) return rc;
-    if ((d->n & 3) != 0) return fail(DADMM_EUNSUPPORTED, "n=%d: needs n %% 4 == 0 (zero-pad n)", d->n);
-    if ((size_t)d->B * d->P * d->n * 4 >= ((size_t)1 << 31))   // 32-bit buffer offsets (gram)
-        return fail(DADMM_EUNSUPPORTED, "B*P*n*4 >= 2^31 bytes per iterate (split the batch)");
+    if ((rc = check_scratch256(scratch)) != DADMM_OK || (rc = check_m(d)) != DADMM_OK ||
+        (rc = check_n4(d)) != DADMM_OK || (rc = check_iterate(d)) != DADMM_OK)   // 32-bit buffer offsets (gram)
+        return rc;
     if (dadmm::adjoint_lds_bytes(d->P) > 160 * 1024 || dadmm::gnn_gram_lds(m_pad_of(d)) > 160 * 1024)
         return fail(DADMM_EUNSUPPORTED, "P=%d / m=%d: the adjoint's LDS tiles do not fit", d->P, d->m);
-    const int np = n_pad_of(d);
     const size_t state = align256(sizeof(float) * (size_t)d->B * d->P * d->n);
     char* base = (char*)scratch;
     dadmm::AdjArgs a{};
-    a.A = (const float*)op;
-    a.At = a.A + (size_t)d->P * m_pad_of(d) * np;
+    fill_args_padded(a, d, op);
     a.vptr = visit_ptr;
     a.vq = visit_q;
     a.deg = deg;
@@ -402,52 +395,21 @@ int dadmm_adjoint(const dadmm_dims* d, const void* op, const int32_t* visit_ptr,
     a.Ub = (float*)(base + state);
     a.Gb = (float*)(base + 2 * state);
     a.partial = (float*)(base + 3 * state);
-    a.B = d->B;
-    a.P = d->P;
-    a.m = d->m;
-    a.m_pad = m_pad_of(d);
-    a.n = d->n;
-    a.n_pad = np;
-    a.K = d->K;
-    a.hyp_rows = d->hyp_rows;
-    a.variant = d->variant;
-    a.graph_shared = d->graph_shared;
-    hipError_t e = dadmm::launch_adjoint(a, dhyp, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "adjoint launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_adjoint(a, dhyp, (hipStream_t)stream), "adjoint launch");
 }
 
 namespace {
 
-int gnn_common(const dadmm_dims* d, dadmm::GnnArgs* a) {
+// the checks every GNN per-iteration entry point starts with, then its arguments from (dims, op);
+// op is NULL for the launches that read no operator (the callers check the pointer afterwards)
+int gnn_common(const dadmm_dims* d, const void* op, dadmm::GnnArgs* a) {
     int rc = check_dims(d);
-    if (rc) return rc;
-    if ((rc = check_m(d)) != DADMM_OK) return rc;
-    if ((d->n & 3) != 0) return fail(DADMM_EUNSUPPORTED, "n=%d: needs n %% 4 == 0 (zero-pad n)", d->n);
-    if ((size_t)d->B * d->P * d->n * 4 >= ((size_t)1 << 31))   // 32-bit buffer offsets (gram)
-        return fail(DADMM_EUNSUPPORTED, "B*P*n*4 >= 2^31 bytes per iterate (split the batch)");
+    if (rc || (rc = check_m(d)) != DADMM_OK || (rc = check_n4(d)) != DADMM_OK ||
+        (rc = check_iterate(d)) != DADMM_OK)   // 32-bit buffer offsets (gram)
+        return rc;
     *a = dadmm::GnnArgs{};
-    a->B = d->B;
-    a->P = d->P;
-    a->m = d->m;
-    a->m_pad = m_pad_of(d);
-    a->n = d->n;
-    a->n_pad = n_pad_of(d);
-    a->K = d->K;
-    a->hyp_rows = d->hyp_rows;
-    a->variant = d->variant;
-    a->graph_shared = d->graph_shared;
+    fill_args_padded(*a, d, op);
     return DADMM_OK;
-}
-
-void set_op(dadmm::GnnArgs* a, const void* op) {
-    a->A = (const float*)op;
-    a->At = a->A + (size_t)a->P * a->m_pad * a->n_pad;
-}
-
-int hip_rc(hipError_t e, const char* what) {
-    if (e != hipSuccess) return fail(DADMM_EHIP, "%s: %s", what, hipGetErrorString(e));
-    return ok();
 }
 
 }  // namespace
@@ -459,38 +421,35 @@ size_t dadmm_gnn_flag_bytes(int32_t K) {
 int dadmm_gnn_begin(const dadmm_dims* d, const void* op, const float* b, const float* y0,
                     const float* U0, float* Atb, int32_t* flags, void* stream) {
     dadmm::GnnArgs a;
-    int rc = gnn_common(d, &a);
+    int rc = gnn_common(d, op, &a);
     if (rc) return rc;
     if (!flags) return fail(DADMM_EINVAL, "flags is NULL");
     if (d->B == 0) return hip_rc(dadmm::gnn_launch_zero(flags, GNN_FLAG_WORDS(d->K), (hipStream_t)stream), "zero launch");
-    if (!op || !b || !y0 || !U0 || !Atb) return fail(DADMM_EINVAL, "a required pointer is NULL");
-    if (!aligned16(op) || !aligned16(y0) || !aligned16(U0) || !aligned16(Atb))
+    if (any_null(op, b, y0, U0, Atb)) return fail(DADMM_EINVAL, "a required pointer is NULL");
+    if (!all_aligned16(op, y0, U0, Atb))
         return fail(DADMM_EINVAL, "op, y0, U0 and Atb must be 16-byte aligned");
-    set_op(&a, op);
     a.b = b;
     a.U = U0;
     a.flags = flags;
-    hipError_t e = dadmm::gnn_launch_zero(flags, GNN_FLAG_WORDS(d->K), (hipStream_t)stream);
-    if (e != hipSuccess) return hip_rc(e, "zero launch");
-    e = dadmm::gnn_launch_check0(a, y0, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_rc(e, "check0 launch");
+    if ((rc = hip_rc(dadmm::gnn_launch_zero(flags, GNN_FLAG_WORDS(d->K), (hipStream_t)stream), "zero launch")) ||
+        (rc = hip_rc(dadmm::gnn_launch_check0(a, y0, (hipStream_t)stream), "check0 launch")))
+        return rc;
     return hip_rc(dadmm::gnn_launch_gram(a, 0, nullptr, Atb, 1, (hipStream_t)stream), "Atb launch");
 }
 
 int dadmm_gnn_gram(const dadmm_dims* d, const void* op, int32_t k, float* const* yptr,
                    const int32_t* flags, const float* x, float* out, void* stream) {
     dadmm::GnnArgs a;
-    int rc = gnn_common(d, &a);
+    int rc = gnn_common(d, op, &a);
     if (rc) return rc;
     if (d->B == 0) return ok();
     if (!op || !out || (x == nullptr && (yptr == nullptr || flags == nullptr)))
         return fail(DADMM_EINVAL, "a required pointer is NULL");
     if (x == nullptr && (k < 0 || k >= d->K)) return fail(DADMM_EINVAL, "k=%d outside [0, K)", k);
-    if (!aligned16(op) || !aligned16(out) || (x && !aligned16(x)))
+    if (!all_aligned16(op, out, x))
         return fail(DADMM_EINVAL, "op, x and out must be 16-byte aligned");
     if (dadmm::gnn_gram_lds(a.m_pad) > 160 * 1024)
         return fail(DADMM_EUNSUPPORTED, "m=%d too large for the gram tile", d->m);
-    set_op(&a, op);
     a.yptr = yptr;
     a.flags = const_cast<int32_t*>(flags);
     return hip_rc(dadmm::gnn_launch_gram(a, k, x, out, 0, (hipStream_t)stream), "gram launch");
@@ -499,16 +458,15 @@ int dadmm_gnn_gram(const dadmm_dims* d, const void* op, int32_t k, float* const*
 int dadmm_gnn_gram_acc(const dadmm_dims* d, const void* op, const float* x, float* out, const float* addend,
                        void* stream) {
     dadmm::GnnArgs a;
-    int rc = gnn_common(d, &a);
+    int rc = gnn_common(d, op, &a);
     if (rc) return rc;
     if (d->B == 0) return ok();
-    if (!op || !out || !x) return fail(DADMM_EINVAL, "a required pointer is NULL");
-    if (!aligned16(op) || !aligned16(out) || !aligned16(x))
+    if (any_null(op, out, x)) return fail(DADMM_EINVAL, "a required pointer is NULL");
+    if (!all_aligned16(op, out, x))
         return fail(DADMM_EINVAL, "op, x and out must be 16-byte aligned");
     if (dadmm::gnn_gram_lds(a.m_pad) > 160 * 1024)
         return fail(DADMM_EUNSUPPORTED, "m=%d too large for the gram tile", d->m);
-    if (addend && !aligned16(addend)) return fail(DADMM_EINVAL, "addend must be 16-byte aligned");
-    set_op(&a, op);
+    if (!aligned16(addend)) return fail(DADMM_EINVAL, "addend must be 16-byte aligned");
     a.acc_add = addend;
     return hip_rc(dadmm::gnn_launch_gram(a, 0, x, out, 2, (hipStream_t)stream), "gram launch");
 }
@@ -518,15 +476,13 @@ int dadmm_gnn_step(const dadmm_dims* d, int32_t k, const int32_t* visit_ptr, con
                    const float* Atb, const float* U, const float* D, float* U_next, float* D_next,
                    float* G, int32_t* flags, void* stream) {
     dadmm::GnnArgs a;
-    int rc = gnn_common(d, &a);
+    int rc = gnn_common(d, nullptr, &a);
     if (rc) return rc;
     if (k < 0 || k >= d->K) return fail(DADMM_EINVAL, "k=%d outside [0, K)", k);
     if (d->B == 0) return ok();
-    if (!visit_ptr || !visit_q || !deg || !hyp_k || !yptr || !AtAy || !Atb || !U || !D || !U_next ||
-        !D_next || !G || !flags)
+    if (any_null(visit_ptr, visit_q, deg, hyp_k, yptr, AtAy, Atb, U, D, U_next, D_next, G, flags))
         return fail(DADMM_EINVAL, "a required pointer is NULL");
-    if (!aligned16(AtAy) || !aligned16(Atb) || !aligned16(U) || !aligned16(D) || !aligned16(G) ||
-        !aligned16(U_next) || !aligned16(D_next))
+    if (!all_aligned16(AtAy, Atb, U, D, G, U_next, D_next))
         return fail(DADMM_EINVAL, "AtAy, Atb, U, D, U_next, D_next and G must be 16-byte aligned");
     a.vptr = visit_ptr;
     a.vq = visit_q;
@@ -547,7 +503,7 @@ int dadmm_gnn_step(const dadmm_dims* d, int32_t k, const int32_t* visit_ptr, con
 int dadmm_gnn_finish(const dadmm_dims* d, float* const* yptr, int32_t* flags, int32_t* status,
                      void* stream) {
     dadmm::GnnArgs a;
-    int rc = gnn_common(d, &a);
+    int rc = gnn_common(d, nullptr, &a);
     if (rc) return rc;
     if (d->K == 0) return ok();
     if (!yptr || !flags) return fail(DADMM_EINVAL, "a required pointer is NULL");
@@ -564,12 +520,11 @@ int dadmm_gnn_step_backward(const dadmm_dims* d, int32_t k, const int32_t* visit
                             float* gy, float* gU, float* gd, float* gAtAy, float* ghyp,
                             void* stream) {
     dadmm::GnnArgs a;
-    int rc = gnn_common(d, &a);
+    int rc = gnn_common(d, nullptr, &a);
     if (rc) return rc;
     if (k < 0 || k >= d->K) return fail(DADMM_EINVAL, "k=%d outside [0, K)", k);
     if (d->B == 0) return ok();
-    if (!visit_ptr || !visit_q || !deg || !hyp_k || !y_k || !AtAy || !Atb || !U || !D || !gy ||
-        !gU || !gd || !gAtAy || !ghyp)
+    if (any_null(visit_ptr, visit_q, deg, hyp_k, y_k, AtAy, Atb, U, D, gy, gU, gd, gAtAy, ghyp))
         return fail(DADMM_EINVAL, "a required pointer is NULL");
     a.vptr = visit_ptr;
     a.vq = visit_q;
@@ -591,12 +546,11 @@ int dadmm_gnn_step_backward_ex(const dadmm_dims* d, int32_t k, const int32_t* vi
                                float* gy, float* gU, float* gd, float* gAtAy, float* ghyp,
                                const dadmm_head_bwd* head, void* stream) {
     dadmm::GnnArgs a;
-    int rc = gnn_common(d, &a);
+    int rc = gnn_common(d, nullptr, &a);
     if (rc) return rc;
     if (k < 0 || k >= d->K) return fail(DADMM_EINVAL, "k=%d outside [0, K)", k);
     if (d->B == 0) return ok();
-    if (!visit_ptr || !visit_q || !deg || !hyp_k || !y_k || !AtAy || !Atb || !U || !D || !gy ||
-        !gU || !gd || !gAtAy || !ghyp)
+    if (any_null(visit_ptr, visit_q, deg, hyp_k, y_k, AtAy, Atb, U, D, gy, gU, gd, gAtAy, ghyp))
         return fail(DADMM_EINVAL, "a required pointer is NULL");
     if (head && (!head->z || !head->dz)) return fail(DADMM_EINVAL, "head: z and dz are required");
     a.vptr = visit_ptr;
@@ -671,9 +625,7 @@ int dadmm_prologue(uint64_t seed, uint64_t offset, int64_t numel, int32_t n, int
     a.d0 = d0;
     a.zero = zero;
     a.nzero = nzero;
-    hipError_t e = dadmm::launch_prologue(a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "prologue launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_prologue(a, (hipStream_t)stream), "prologue launch");
 }
 
 
@@ -688,9 +640,7 @@ int dadmm_graph_generate(int32_t B, int32_t P, float prob, uint64_t seed, int32_
     if ((int64_t)B * 2 * P * (P - 1) >= ((int64_t)1 << 31))
         return fail(DADMM_EUNSUPPORTED, "visit lists past 2^31 entries (split the batch)");
     dadmm::GraphGenArgs a{B, P, prob, seed, connect ? 1 : 0, nbr, deg, order, scratch, vptr, vq};
-    hipError_t e = dadmm::launch_graphgen(a, vq == nullptr ? 0 : 1, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "graph generation launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_graphgen(a, vq == nullptr ? 0 : 1, (hipStream_t)stream), "graph generation launch");
 }
 
 size_t dadmm_tiled_scratch_bytes(const dadmm_dims* d) {
@@ -708,25 +658,20 @@ static int forward_tiled_impl(const dadmm_dims* d, const void* op, const float* 
     int rc = check_dims(d);
     if (rc) return rc;
     if (d->B == 0 || d->K == 0) return ok();
-    if (!op || !b || !visit_ptr || !visit_q || !deg || !hyp || !y0 || !U0 || !d0 || !Y || !scratch)
+    if (any_null(op, b, visit_ptr, visit_q, deg, hyp, y0, U0, d0, Y, scratch))
         return fail(DADMM_EINVAL, "a required pointer is NULL");
-    if (!aligned16(op) || !aligned16(Y) || !aligned16(y0) || !aligned16(U0) || !aligned16(d0) ||
-        (U_out != nullptr && !aligned16(U_out)))
+    if (!all_aligned16(op, Y, y0, U0, d0, U_out))
         return fail(DADMM_EINVAL, "op, Y, y0, U0, d0 and U_out must be 16-byte aligned");
-    if (((uintptr_t)scratch & 255u) != 0) return fail(DADMM_EINVAL, "scratch must be 256-byte aligned");
+    if ((rc = check_scratch256(scratch)) != DADMM_OK) return rc;
     if (m_pad_of(d) > 2 * dadmm::M_PAD)   // iter_kernel<MB>: MB in {1, 2}
         return fail(DADMM_EUNSUPPORTED, "m=%d > %d rows per agent: not a tiled shape", d->m,
                     2 * dadmm::M_PAD);
-    if ((d->n & 3) != 0) return fail(DADMM_EUNSUPPORTED, "n=%d: needs n %% 4 == 0 (zero-pad n)", d->n);
-    if ((size_t)d->B * d->P * d->n * 4 >= ((size_t)1 << 31))
-        return fail(DADMM_EUNSUPPORTED, "B*P*n*4 >= 2^31 bytes per iterate (split the batch)");
-    const int np = n_pad_of(d);
-    if (dadmm::tiled_lds_bytes(np, m_pad_of(d)) > 160 * 1024)
+    if ((rc = check_n4(d)) != DADMM_OK || (rc = check_iterate(d)) != DADMM_OK) return rc;
+    if (dadmm::tiled_lds_bytes(n_pad_of(d), m_pad_of(d)) > 160 * 1024)
         return fail(DADMM_EUNSUPPORTED, "n=%d: the y tile does not fit the LDS", d->n);
     const size_t state = align256(sizeof(float) * (size_t)d->B * d->P * d->n);
     dadmm::TiledArgs a{};
-    a.A = (const float*)op;
-    a.At = a.A + (size_t)d->P * m_pad_of(d) * np;
+    fill_args_padded(a, d, op);
     a.b = b;
     a.vptr = visit_ptr;
     a.vq = visit_q;
@@ -742,18 +687,8 @@ static int forward_tiled_impl(const dadmm_dims* d, const void* op, const float* 
     a.R = (float*)((char*)scratch + 3 * state);
     a.U_out = U_out;
     a.status = status;
-    a.B = d->B;
-    a.P = d->P;
-    a.m = d->m;
-    a.m_pad = m_pad_of(d);
-    a.n = d->n;
-    a.n_pad = np;
-    a.K = d->K;
-    a.hyp_rows = d->hyp_rows;
-    a.variant = d->variant;
-    a.graph_shared = d->graph_shared;
     if (Grec != nullptr || Urec != nullptr) {   // recording: the streamed single-launch form only
-        if (Grec == nullptr || Urec == nullptr || !aligned16(Grec) || !aligned16(Urec))
+        if (any_null(Grec, Urec) || !all_aligned16(Grec, Urec))
             return fail(DADMM_EINVAL, "Grec and Urec: both, 16-byte aligned");
         if ((size_t)d->K * d->B * d->P * d->n * 4 >= ((size_t)1 << 40))
             return fail(DADMM_EINVAL, "recording too large");
@@ -762,13 +697,9 @@ static int forward_tiled_impl(const dadmm_dims* d, const void* op, const float* 
         if (!dadmm::stream_applies(a))
             return fail(DADMM_EUNSUPPORTED, "recording on the tiled path needs the streamed form (P <= 16, "
                                             "m <= 64, n_pad >= 128): use dadmm_forward_stepwise");
-        hipError_t e = dadmm::launch_stream(a, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(DADMM_EHIP, "streamed recording launch: %s", hipGetErrorString(e));
-        return ok();
+        return hip_rc(dadmm::launch_stream(a, (hipStream_t)stream), "streamed recording launch");
     }
-    hipError_t e = dadmm::launch_tiled(a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "tiled launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_tiled(a, (hipStream_t)stream), "tiled launch");
 }
 
 int dadmm_forward_tiled(const dadmm_dims* d, const void* op, const float* b,
@@ -823,9 +754,7 @@ int dadmm_loss(int32_t K, int32_t B, int32_t P, int32_t n, int32_t n_store, cons
     a.losses = losses;
     a.out = out;
     a.flags = flags;
-    hipError_t e = dadmm::launch_loss(a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "loss launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_loss(a, (hipStream_t)stream), "loss launch");
 }
 
 int dadmm_loss_grad(int32_t K, int32_t B, int32_t P, int32_t n, int32_t n_store, const float* Y,
@@ -836,9 +765,7 @@ int dadmm_loss_grad(int32_t K, int32_t B, int32_t P, int32_t n, int32_t n_store,
     if (rc) return rc;
     if (!flags || !gout || !dY) return fail(DADMM_EINVAL, "a required pointer is NULL");
     a.flags = const_cast<int32_t*>(flags);
-    hipError_t e = dadmm::launch_loss_grad(a, gout, dY, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "loss grad launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_loss_grad(a, gout, dY, (hipStream_t)stream), "loss grad launch");
 }
 
 static int hyper_input(int32_t rows, int32_t K, int32_t N, const float* x1, int32_t ld1, int32_t K1,
@@ -884,9 +811,7 @@ int dadmm_hyper_linear(int32_t rows, int32_t K, int32_t N, const float* x1, int3
     a.P = 1;
     a.B = rows;
     a.splits = 1;
-    hipError_t e = dadmm::launch_hyper(a, HYPER_EPI_BIAS, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "linear launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_hyper(a, HYPER_EPI_BIAS, (hipStream_t)stream), "linear launch");
 }
 
 static int hyper_linear_ex_kw(int32_t kwave, int32_t rows, int32_t K, int32_t N, const float* x1, int32_t ld1,
@@ -903,9 +828,7 @@ static int hyper_linear_ex_kw(int32_t kwave, int32_t rows, int32_t K, int32_t N,
     a.B = rows;
     a.splits = 1;
     a.kwave = kwave;
-    hipError_t e = dadmm::launch_hyper(a, HYPER_EPI_BIAS, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "linear launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_hyper(a, HYPER_EPI_BIAS, (hipStream_t)stream), "linear launch");
 }
 
 int dadmm_hyper_linear_ex(int32_t rows, int32_t K, int32_t N, const float* x1, int32_t ld1, int32_t K1,
@@ -947,9 +870,7 @@ int dadmm_hyper_gcn(int32_t B, int32_t P, int32_t K, int32_t N, const float* x1,
     a.bn_b = bn_bias;
     a.bn_eps = bn_eps;
     a.slope = slope;
-    hipError_t e = dadmm::launch_hyper(a, HYPER_EPI_GCN, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "gcn launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_hyper(a, HYPER_EPI_GCN, (hipStream_t)stream), "gcn launch");
 }
 
 int dadmm_hyper_gcn_ex(int32_t B, int32_t P, int32_t K, int32_t N, const float* x, int32_t ldx,
@@ -982,9 +903,7 @@ int dadmm_hyper_gcn_ex(int32_t B, int32_t P, int32_t K, int32_t N, const float* 
     a.bn_b = bn_bias;
     a.bn_eps = bn_eps;
     a.slope = slope;
-    hipError_t e = dadmm::launch_hyper(a, HYPER_EPI_GCN, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "gcn launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_hyper(a, HYPER_EPI_GCN, (hipStream_t)stream), "gcn launch");
 }
 
 int dadmm_hyper_head(int32_t B, int32_t K, int32_t H, const float* x, int32_t ldx, const float* W,
@@ -1003,9 +922,7 @@ int dadmm_hyper_head(int32_t B, int32_t K, int32_t H, const float* x, int32_t ld
     a.maxv[1] = tau_max;
     a.maxv[2] = rho_max;
     a.maxv[3] = eta_max;
-    hipError_t e = dadmm::launch_hyper(a, HYPER_EPI_HEAD, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "head launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_hyper(a, HYPER_EPI_HEAD, (hipStream_t)stream), "head launch");
 }
 
 int dadmm_hyper_head_train(int32_t B, int32_t K, int32_t H, const float* x, int32_t ldx, const float* W,
@@ -1026,9 +943,7 @@ int dadmm_hyper_head_train(int32_t B, int32_t K, int32_t H, const float* x, int3
     a.maxv[2] = rho_max;
     a.maxv[3] = eta_max;
     a.save_m = z;
-    hipError_t e = dadmm::launch_hyper(a, HYPER_EPI_HEAD, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "head launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_hyper(a, HYPER_EPI_HEAD, (hipStream_t)stream), "head launch");
 }
 
 int dadmm_hyper_rownorm(int32_t rows, int32_t C, const float* x, const float* weight,
@@ -1040,9 +955,7 @@ int dadmm_hyper_rownorm(int32_t rows, int32_t C, const float* x, const float* we
     if (!aligned16(x) || !aligned16(weight) || !aligned16(bias) || !aligned16(y))
         return fail(DADMM_EINVAL, "rownorm operands must be 16-byte aligned");
     dadmm::RowNormArgs a{x, weight, bias, y, rows, C, act ? 1 : 0, eps, slope, 1, 0, nullptr};
-    hipError_t e = dadmm::launch_rownorm(a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "rownorm launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_rownorm(a, (hipStream_t)stream), "rownorm launch");
 }
 
 size_t dadmm_hyper_linear_ln_scratch_bytes(int32_t rows, int32_t K, int32_t N) {
@@ -1069,13 +982,10 @@ int dadmm_hyper_linear_ln(int32_t rows, int32_t K, int32_t N, const float* x, in
     a.ldy = N;
     a.P = 1;
     a.B = rows;
-    hipError_t e = dadmm::launch_hyper(a, HYPER_EPI_BIAS, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "linear launch: %s", hipGetErrorString(e));
+    if ((rc = hip_rc(dadmm::launch_hyper(a, HYPER_EPI_BIAS, (hipStream_t)stream), "linear launch"))) return rc;
     dadmm::RowNormArgs r{(const float*)scratch, ln_weight, ln_bias, y, rows, N, act ? 1 : 0, eps,
                          slope, a.splits, a.split_stride, bias};
-    e = dadmm::launch_rownorm(r, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "rownorm launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_rownorm(r, (hipStream_t)stream), "rownorm launch");
 }
 
 int dadmm_hyper_gcn_train(int32_t B, int32_t P, int32_t K, int32_t N, const float* x1, int32_t ld1,
@@ -1138,9 +1048,7 @@ int dadmm::gcn_train_impl(int32_t B, int32_t P, int32_t K, int32_t N, const floa
         return fail(DADMM_EINVAL, "addend: ld_add=%d < N=%d or misaligned", ld_add, N);
     a.addend = addend;
     a.ld_add = ld_add;
-    hipError_t e = dadmm::launch_hyper(a, HYPER_EPI_GCN_TRAIN, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "gcn train launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_hyper(a, HYPER_EPI_GCN_TRAIN, (hipStream_t)stream), "gcn train launch");
 }
 
 extern "C" {
@@ -1196,9 +1104,7 @@ int dadmm_hyper_bn_running_update(int32_t layers, const int32_t* widths, float* 
     a.decay = decay;
     a.part = (double*)scratch;
     a.splits = bn_running_splits(iters, B);
-    hipError_t e = dadmm::launch_bn_running(a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "BatchNorm running-statistics launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_bn_running(a, (hipStream_t)stream), "BatchNorm running-statistics launch");
 }
 
 int dadmm_hyper_gcn_train_bwd(int32_t B, int32_t P, int32_t N, const float* dy, const float* m,
@@ -1212,9 +1118,7 @@ int dadmm_hyper_gcn_train_bwd(int32_t B, int32_t P, int32_t N, const float* dy, 
     if ((int64_t)B * P * N >= ((int64_t)1 << 31)) return fail(DADMM_EUNSUPPORTED, "operand larger than 2^31 floats");
     dadmm::GcnBwdArgs a{dy, m, mean, var, bn_weight, ahat, ahat_per_sample ? 1 : 0, dz, part, B, P, N,
                         bn_eps, slope, drop_p, seed, site, bn_eval ? 1 : 0};
-    hipError_t e = dadmm::launch_gcn_bwd(a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "gcn backward launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_gcn_bwd(a, (hipStream_t)stream), "gcn backward launch");
 }
 
 int dadmm_hyper_linear_gcn_bwd(int32_t B, int32_t P, int32_t K, int32_t N, const float* x, int32_t ldx,
@@ -1248,9 +1152,7 @@ int dadmm_hyper_linear_gcn_bwd(int32_t B, int32_t P, int32_t K, int32_t N, const
     a.site = site;
     a.part = part;
     a.bn_eval = bn_eval ? 1 : 0;
-    hipError_t e = dadmm::launch_hyper(a, HYPER_EPI_GCN_BWD, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "linear + gcn backward launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_hyper(a, HYPER_EPI_GCN_BWD, (hipStream_t)stream), "linear + gcn backward launch");
 }
 
 int dadmm_hyper_linear_ln_train(int32_t rows, int32_t K, int32_t N, const float* x, int32_t ldx,
@@ -1274,13 +1176,10 @@ int dadmm_hyper_linear_ln_train(int32_t rows, int32_t K, int32_t N, const float*
     a.ldy = N;
     a.P = 1;
     a.B = rows;
-    hipError_t e = dadmm::launch_hyper(a, HYPER_EPI_BIAS, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "linear launch: %s", hipGetErrorString(e));
+    if ((rc = hip_rc(dadmm::launch_hyper(a, HYPER_EPI_BIAS, (hipStream_t)stream), "linear launch"))) return rc;
     dadmm::RowNormArgs r{(const float*)scratch, ln_weight, ln_bias, y, rows, N, act ? 1 : 0, eps,
                          slope, a.splits, a.split_stride, bias, drop_p, seed, site, xd};
-    e = dadmm::launch_rownorm(r, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "rownorm launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_rownorm(r, (hipStream_t)stream), "rownorm launch");
 }
 
 size_t dadmm_hyper_rownorm_bwd_part_bytes(int32_t rows, int32_t C) {
@@ -1299,9 +1198,7 @@ int dadmm_hyper_rownorm_bwd(int32_t rows, int32_t C, const float* dy, const floa
         return fail(DADMM_EINVAL, "rownorm operands must be 16-byte aligned");
     dadmm::RowNormBwdArgs a{dy, xd, weight, bias, dx, part, rows, C, act ? 1 : 0, eps, slope, drop_p,
                             seed, site};
-    hipError_t e = dadmm::launch_rownorm_bwd(a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "rownorm backward launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_rownorm_bwd(a, (hipStream_t)stream), "rownorm backward launch");
 }
 
 int dadmm_hyper_head_act(int32_t mode, int32_t B, int32_t H, const float* z, const float* dhyp,
@@ -1310,9 +1207,7 @@ int dadmm_hyper_head_act(int32_t mode, int32_t B, int32_t H, const float* z, con
     if (B < 0 || H < 1 || (mode != 0 && mode != 1)) return fail(DADMM_EINVAL, "bad head dims/mode");
     if (!z || !out || (mode == 1 && !dhyp)) return fail(DADMM_EINVAL, "a required pointer is NULL");
     const float mx[4] = {alpha_max, tau_max, rho_max, eta_max};
-    hipError_t e = dadmm::launch_head_act(mode, B, H, z, dhyp, mx, out, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "head launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_head_act(mode, B, H, z, dhyp, mx, out, (hipStream_t)stream), "head launch");
 }
 
 size_t dadmm_hyper_wgrad_scratch_bytes(int32_t R, int32_t N, int32_t K) {
@@ -1336,17 +1231,14 @@ int dadmm_hyper_wgrad(int32_t R, int32_t N, int32_t K, const float* dz, int32_t 
         if (beta) return ok();
         hipError_t e = hipMemsetAsync(g, 0, 4 * (size_t)N * K, (hipStream_t)stream);
         if (e == hipSuccess && gbias) e = hipMemsetAsync(gbias, 0, 4 * (size_t)N, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(DADMM_EHIP, "memset: %s", hipGetErrorString(e));
-        return ok();
+        return hip_rc(e, "memset");
     }
     // scratch: [splits][N][K] partial tiles, [splits][N] partial bias sums
     float* part = splits > 1 ? (float*)scratch : nullptr;
     dadmm::WgradArgs a{dz, x1, K1 < K ? x2 : x1, g, gbias, part,
                        splits > 1 ? part + (size_t)splits * N * K : nullptr,
                        R, N, K, K1, ldz, ld1, K1 < K ? ld2 : ld1, splits, beta ? 1 : 0};
-    hipError_t e = dadmm::launch_wgrad(a, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "wgrad launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_wgrad(a, (hipStream_t)stream), "wgrad launch");
 }
 
 int dadmm_hyper_colsum(const float* part, int32_t G, int32_t R, int32_t C, float* out, int32_t beta,
@@ -1354,9 +1246,7 @@ int dadmm_hyper_colsum(const float* part, int32_t G, int32_t R, int32_t C, float
     if (G < 1 || R < 0 || C < 1) return fail(DADMM_EINVAL, "bad colsum dims G=%d R=%d C=%d", G, R, C);
     if (!out || (R > 0 && !part)) return fail(DADMM_EINVAL, "a required pointer is NULL");
     if ((int64_t)G * R * C >= ((int64_t)1 << 31)) return fail(DADMM_EUNSUPPORTED, "operand larger than 2^31 floats");
-    hipError_t e = dadmm::launch_colsum(part, G, R, C, out, beta ? 1 : 0, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "colsum launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_colsum(part, G, R, C, out, beta ? 1 : 0, (hipStream_t)stream), "colsum launch");
 }
 
 int dadmm_hyper_transpose(int32_t rows, int32_t cols, const float* in, float* out, void* stream) {
@@ -1364,9 +1254,7 @@ int dadmm_hyper_transpose(int32_t rows, int32_t cols, const float* in, float* ou
     if (rows == 0 || cols == 0) return ok();
     if (!in || !out) return fail(DADMM_EINVAL, "a required pointer is NULL");
     if ((int64_t)rows * cols >= ((int64_t)1 << 31)) return fail(DADMM_EUNSUPPORTED, "operand larger than 2^31 floats");
-    hipError_t e = dadmm::launch_transpose(in, rows, cols, out, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "transpose launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_transpose(in, rows, cols, out, (hipStream_t)stream), "transpose launch");
 }
 
 size_t dadmm_stepwise_scratch_bytes(const dadmm_dims* d) {
@@ -1386,25 +1274,20 @@ int dadmm_forward_stepwise(const dadmm_dims* d, const void* op, const float* b,
     if ((gate & DADMM_GATE_ON) && status == nullptr)
         return fail(DADMM_EINVAL, "DADMM_GATE_ON needs the status word");
     if (d->B == 0 || d->K == 0) return ok();
-    if (!op || !b || !visit_ptr || !visit_q || !deg || !hyp || !y0 || !U0 || !d0 || !Y || !scratch)
+    if (any_null(op, b, visit_ptr, visit_q, deg, hyp, y0, U0, d0, Y, scratch))
         return fail(DADMM_EINVAL, "a required pointer is NULL");
-    if (!aligned16(op) || !aligned16(Y) || !aligned16(y0) || !aligned16(U0) || !aligned16(d0) ||
-        (U_out != nullptr && !aligned16(U_out)))
+    if (!all_aligned16(op, Y, y0, U0, d0, U_out))
         return fail(DADMM_EINVAL, "op, Y, y0, U0, d0 and U_out must be 16-byte aligned");
-    if (((uintptr_t)scratch & 255u) != 0) return fail(DADMM_EINVAL, "scratch must be 256-byte aligned");
+    if ((rc = check_scratch256(scratch)) != DADMM_OK) return rc;
     if ((Grec == nullptr) != (Urec == nullptr))
         return fail(DADMM_EINVAL, "Grec and Urec: both or neither");
-    if (Grec != nullptr && (!aligned16(Grec) || !aligned16(Urec)))
+    if (!all_aligned16(Grec, Urec))
         return fail(DADMM_EINVAL, "Grec and Urec must be 16-byte aligned");
-    if ((rc = check_m(d)) != DADMM_OK) return rc;
-    if ((d->n & 3) != 0)
-        return fail(DADMM_EUNSUPPORTED, "n=%d: needs n %% 4 == 0 (zero-pad n)", d->n);
+    if ((rc = check_m(d)) != DADMM_OK || (rc = check_n4(d)) != DADMM_OK) return rc;
     const size_t state = align256(sizeof(float) * (size_t)d->B * d->P * d->n);
     char* base = (char*)scratch + align256(dadmm::stepwise_flag_bytes(d->K));
-    const int np = n_pad_of(d);
     dadmm::StepArgs a;
-    a.A = (const float*)op;
-    a.At = a.A + (size_t)d->P * m_pad_of(d) * np;
+    fill_args_padded(a, d, op);
     a.b = b;
     a.vptr = visit_ptr;
     a.vq = visit_q;
@@ -1421,20 +1304,8 @@ int dadmm_forward_stepwise(const dadmm_dims* d, const void* op, const float* b,
     a.status = status;
     a.Grec = Grec;
     a.Urec = Urec;
-    a.B = d->B;
-    a.P = d->P;
-    a.m = d->m;
-    a.m_pad = m_pad_of(d);
-    a.n = d->n;
-    a.n_pad = np;
-    a.K = d->K;
-    a.hyp_rows = d->hyp_rows;
-    a.variant = d->variant;
-    a.graph_shared = d->graph_shared;
-    hipError_t e = dadmm::launch_stepwise(a, gate & DADMM_GATE_ON, (gate & DADMM_FLAGS_ZEROED) != 0,
-                                          (hipStream_t)stream);
-    if (e != hipSuccess) return fail(DADMM_EHIP, "stepwise launch: %s", hipGetErrorString(e));
-    return ok();
+    return hip_rc(dadmm::launch_stepwise(a, gate & DADMM_GATE_ON, (gate & DADMM_FLAGS_ZEROED) != 0, (hipStream_t)stream),
+                  "stepwise launch");
 }
 
 }  // extern "C"

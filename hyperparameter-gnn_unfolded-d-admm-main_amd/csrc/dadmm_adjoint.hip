@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dadmm_device.h"
 #include "dadmm_internal.h"
 
 namespace dadmm {
@@ -28,21 +29,7 @@ namespace adj {
 
 constexpr int THREADS = 256;   // 4 waves, one (sample, 64-column) item each
 constexpr int WAVES = 4;
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 // the register-resident update runs in the 16-byte-lane form (adj_update_v4)
-
-__device__ __forceinline__ float tclamp(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
-__device__ __forceinline__ bool inside(float x, float lo, float hi) { return x >= lo && x <= hi; }
-
-__device__ __forceinline__ void clips(int variant, int k, float& gclip, float& vclip) {
-    if (variant == 0) {
-        gclip = fmaxf(1.0f, 30.0f - (float)k);          // unfolded_DLASSO.py:80
-        vclip = fmaxf(10.0f, 200.0f - (float)(k * 3));  // unfolded_DLASSO.py:92
-    } else {
-        gclip = 10.0f;                                   // gnn_dlasso_models_progressive.py:212
-        vclip = 100.0f;                                  // :224, :232
-    }
-}
 
 // sum over p's visit list of (x_p - x_q): compute_delta's accumulation order (:127-140). The
 // sample's list starts vp [P + 1] (relative) and entries vq sit in this wave's LDS slice: the
@@ -93,7 +80,7 @@ __global__ __launch_bounds__(64 * W) void adj_update_kernel(AdjArgs a, int k, in
             for (int i = lane; i < ve - v0; i += 64) vql[i] = a.vq[v0 + i];
         }
         float gclip, vclip;
-        clips(a.variant, k, gclip, vclip);
+        iter_clips(a.variant, k, gclip, vclip);
         auto hyp = [&](int kk, int p, int comp) {
             return a.hyp[((size_t)kk * H + (H == 1 ? 0 : p)) * 4 + comp];
         };
@@ -135,8 +122,8 @@ __global__ __launch_bounds__(64 * W) void adj_update_kernel(AdjArgs a, int k, in
             for (int i = 0; i < GP; ++i) {
                 const int p = p0 + i;
                 if (p >= P) break;
-                const bool md = a.variant == 0 || inside(d1[i], -20.0f, 20.0f);   // GNN clamp :229
-                const float dcl = a.variant == 0 ? d1[i] : tclamp(d1[i], -20.0f, 20.0f);
+                const bool md = a.variant == 0 || inside(d1[i], -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);   // GNN clamp :229
+                const float dcl = a.variant == 0 ? d1[i] : tclamp(d1[i], -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);
                 float pe = 0.0f, db = 0.0f;
                 if (cv) {
                     const size_t off = base + (size_t)p * n;
@@ -168,7 +155,7 @@ __global__ __launch_bounds__(64 * W) void adj_update_kernel(AdjArgs a, int k, in
                     tv[i] = visit_sum(ds, vpl, vql, p, lane);
                     if (k > 0) {
                         dk[i] = visit_sum(xs, vpl, vql, p, lane);
-                        if (a.variant != 0) dk[i] = tclamp(dk[i], -20.0f, 20.0f);
+                        if (a.variant != 0) dk[i] = tclamp(dk[i], -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);
                     }
                 }
             }
@@ -229,13 +216,13 @@ __global__ __launch_bounds__(64 * W) void adj_update_kernel(AdjArgs a, int k, in
 // the LDS rows are read as b128 (a 16-lane group spans 16 distinct 16-byte bank slots). Every
 // element's value and operation order is the generic kernel's; only the dhyp partial sums are
 // associated differently (each lane's 4 columns, then a 16-lane shuffle tree per agent).
-__device__ __forceinline__ f32x4v visit_sum4(const float* __restrict__ x, const int32_t* __restrict__ vp,
+__device__ __forceinline__ f32x4 visit_sum4(const float* __restrict__ x, const int32_t* __restrict__ vp,
                                              const uint8_t* __restrict__ vq, int p, int cq) {
-    const f32x4v xp = *(const f32x4v*)(x + p * 64 + 4 * cq);
-    f32x4v acc = {0.0f, 0.0f, 0.0f, 0.0f};
+    const f32x4 xp = *(const f32x4*)(x + p * 64 + 4 * cq);
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
     const int t1 = vp[p + 1];
     for (int t = vp[p]; t < t1; ++t) {
-        const f32x4v xq = *(const f32x4v*)(x + (int)vq[t] * 64 + 4 * cq);
+        const f32x4 xq = *(const f32x4*)(x + (int)vq[t] * 64 + 4 * cq);
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[r] = acc[r] + (xp[r] - xq[r]);
     }
@@ -243,7 +230,7 @@ __device__ __forceinline__ f32x4v visit_sum4(const float* __restrict__ x, const 
 }
 
 // sum of v over this lane's 4 columns and its 16-lane group -> red[p][c] (lane 16 a adds)
-__device__ __forceinline__ void group_accum(float* red, int p, int c, f32x4v v, bool live, int lane) {
+__device__ __forceinline__ void group_accum(float* red, int p, int c, f32x4 v, bool live, int lane) {
     float s = (v[0] + v[1]) + (v[2] + v[3]);
     s = row16_sum_dpp(s);
     if ((lane & 15) == 0 && live) red[p * 4 + c] += s;
@@ -276,17 +263,17 @@ __global__ __launch_bounds__(THREADS) void adj_update_v4(AdjArgs a, int k, int i
             for (int i = lane; i < ve - v0; i += 64) vql[i] = a.vq[v0 + i];
         }
         float gclip, vclip;
-        clips(a.variant, k, gclip, vclip);
+        iter_clips(a.variant, k, gclip, vclip);
         auto hyp = [&](int kk, int p, int comp) {
             return a.hyp[((size_t)kk * H + (H == 1 ? 0 : p)) * 4 + comp];
         };
         auto off_of = [&](int p) { return (size_t)s * P * n + (size_t)p * n + (cv ? c : 0); };
-        const f32x4v z4 = {0.0f, 0.0f, 0.0f, 0.0f};
+        const f32x4 z4 = {0.0f, 0.0f, 0.0f, 0.0f};
         auto ld = [&](const float* __restrict__ base, int p) {
-            return (cv && p < P) ? *(const f32x4v*)(base + off_of(p)) : z4;
+            return (cv && p < P) ? *(const f32x4*)(base + off_of(p)) : z4;
         };
-        auto st = [&](float* __restrict__ base, int p, f32x4v v) {
-            if (cv && p < P) *(f32x4v*)(base + off_of(p)) = v;
+        auto st = [&](float* __restrict__ base, int p, f32x4 v) {
+            if (cv && p < P) *(f32x4*)(base + off_of(p)) = v;
         };
         const float* __restrict__ y1 = a.Y + (size_t)k * S;
         const float* __restrict__ yk = k > 0 ? a.Y + (size_t)(k - 1) * S : a.y0;
@@ -299,11 +286,11 @@ __global__ __launch_bounds__(THREADS) void adj_update_v4(AdjArgs a, int k, int i
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
             const int p = 4 * g + ag;
-            if (4 * g < P && p < P) *(f32x4v*)(xs + p * 64 + 4 * cq) = ld(y1, p);
+            if (4 * g < P && p < P) *(f32x4*)(xs + p * 64 + 4 * cq) = ld(y1, p);
         }
         // the second phase's operands (y_k rows, Grec[k]) issued now, so that phase
         // does not start with another HBM round trip
-        f32x4v ykr[NG], grr[NG];
+        f32x4 ykr[NG], grr[NG];
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
             ykr[g] = ld(yk, 4 * g + ag);
@@ -311,7 +298,7 @@ __global__ __launch_bounds__(THREADS) void adj_update_v4(AdjArgs a, int k, int i
         }
     
         __builtin_amdgcn_wave_barrier();
-        f32x4v ybr[NG], ubr[NG];
+        f32x4 ybr[NG], ubr[NG];
         // dual-update adjoint of iteration k (:95-99): the group's loads in flight together, then
         // the visit sums (LDS) under them
 #pragma unroll
@@ -319,18 +306,18 @@ __global__ __launch_bounds__(THREADS) void adj_update_v4(AdjArgs a, int k, int i
             ybr[g] = ubr[g] = z4;
             if (4 * g >= P) continue;
             const int p = 4 * g + ag;
-            const f32x4v gy = ld(gYk, p), ur = ld(Urk, p), gb = ld(Gbs, p);
+            const f32x4 gy = ld(gYk, p), ur = ld(Urk, p), gb = ld(Gbs, p);
             ubr[g] = ld(Ubs, p);
             ybr[g] = ld(ybs, p);
             const bool pv = p < P;
-            const f32x4v d1 = pv ? visit_sum4(xs, vpl, vql, p, cq) : z4;
+            const f32x4 d1 = pv ? visit_sum4(xs, vpl, vql, p, cq) : z4;
             const float et = hyp(k, pv ? p : 0, 3);
             const float rh1 = k + 1 < K ? hyp(k + 1, pv ? p : 0, 2) : 0.0f;
-            f32x4v pe = z4, db = z4;
+            f32x4 pe = z4, db = z4;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const bool md = a.variant == 0 || inside(d1[r], -20.0f, 20.0f);   // GNN clamp :229
-                const float dcl = a.variant == 0 ? d1[r] : tclamp(d1[r], -20.0f, 20.0f);
+                const bool md = a.variant == 0 || inside(d1[r], -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);   // GNN clamp :229
+                const float dcl = a.variant == 0 ? d1[r] : tclamp(d1[r], -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);
                 ybr[g][r] = ybr[g][r] + gy[r];                                   // + gY[k]
                 const float wv = ur[r] + dcl * et;
                 const float wb = inside(wv, -vclip, vclip) ? ubr[g][r] : 0.0f;
@@ -339,14 +326,14 @@ __global__ __launch_bounds__(THREADS) void adj_update_v4(AdjArgs a, int k, int i
                 ubr[g][r] = wb;
             }
             if (!cv) pe = db = z4;
-            if (pv) *(f32x4v*)(ds + p * 64 + 4 * cq) = db;
+            if (pv) *(f32x4*)(ds + p * 64 + 4 * cq) = db;
             group_accum(rw, pv ? p : 0, 3, pe, pv, lane);
         }
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
             const int p = 4 * g + ag;
-            if (4 * g < P && p < P) *(f32x4v*)(xs + p * 64 + 4 * cq) = ykr[g];
+            if (4 * g < P && p < P) *(f32x4*)(xs + p * 64 + 4 * cq) = ykr[g];
         }
         __builtin_amdgcn_wave_barrier();
         // y_bar += 2 L d_bar; primal-update and gradient-clamp adjoint (:73-93)
@@ -356,20 +343,20 @@ __global__ __launch_bounds__(THREADS) void adj_update_v4(AdjArgs a, int k, int i
             const int p = 4 * g + ag;
             const bool pv = p < P;
             const int pc = pv ? p : 0;
-            const f32x4v gr = grr[g];
-            f32x4v dk = k == 0 ? ld(a.d0, p) : z4;
-            const f32x4v tv = pv ? visit_sum4(ds, vpl, vql, p, cq) : z4;
+            const f32x4 gr = grr[g];
+            f32x4 dk = k == 0 ? ld(a.d0, p) : z4;
+            const f32x4 tv = pv ? visit_sum4(ds, vpl, vql, p, cq) : z4;
             if (k > 0 && pv) {
                 dk = visit_sum4(xs, vpl, vql, p, cq);
                 if (a.variant != 0) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) dk[r] = tclamp(dk[r], -20.0f, 20.0f);
+                    for (int r = 0; r < 4; ++r) dk[r] = tclamp(dk[r], -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);
                 }
             }
             const float al = hyp(k, pc, 0);
             const float dg = a.deg[g0 + pc];
-            const f32x4v y = *(const f32x4v*)(xs + pc * 64 + 4 * cq);
-            f32x4v pa = z4, pt = z4, pr = z4, ubn, zbv, grbv;
+            const f32x4 y = *(const f32x4*)(xs + pc * 64 + 4 * cq);
+            f32x4 pa = z4, pt = z4, pr = z4, ubn, zbv, grbv;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float gv = tclamp(gr[r], -gclip, gclip);

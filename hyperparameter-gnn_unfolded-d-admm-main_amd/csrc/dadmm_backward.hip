@@ -31,34 +31,11 @@
 #include <stdint.h>
 
 #include "dadmm_consensus.h"
+#include "dadmm_device.h"
 #include "dadmm_internal.h"
 
 namespace dadmm {
 namespace bwd {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ rsrc_t make_rsrc(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ f32x4 bload4(rsrc_t r, uint32_t voff, uint32_t soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-__device__ __forceinline__ float tclamp(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
-__device__ __forceinline__ bool inside(float x, float lo, float hi) { return x >= lo && x <= hi; }
-typedef const __attribute__((address_space(4))) float cfloat;
-// compiler-only barrier: bounds how far the scheduler hoists loads (register budget)
-__device__ __forceinline__ void fence() { asm volatile("" ::: "memory"); }
-// a per-iteration opaque copy of a wave-uniform value: keeps the shared graph's neighbour tests
-// inside the loop (s_bitcmp + branch) instead of P*P hoisted 64-bit condition registers
-__device__ __forceinline__ uint32_t fresh_s(uint32_t x) {
-    asm volatile("" : "=s"(x) : "0"(x));
-    return x;
-}
 
 // Decisions measured at H (round 6 removed the A/B switches):
 //   * 4 waves per workgroup (one per SIMD, 512 registers: twice the rows per wave, room for more of
@@ -77,17 +54,6 @@ __device__ __forceinline__ uint32_t fresh_s(uint32_t x) {
 //   * the per-iteration dhyp wave sums on DPP moves (wave_sum_dpp): a fixed order, deterministic.
 constexpr int WAVES = 4;
 #define BWD_ROW(e, r) (r)
-typedef __attribute__((address_space(3))) void lds_void;
-__device__ __forceinline__ void wait_vm(int n) {   // s_waitcnt vmcnt(n), n folded at compile time
-    switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    }
-}
-
 // GNN variant: delta = clamp(delta, -20, 20) (gnn_dlasso_models_progressive.py:229) in place;
 // returns bit 4p+r set where the pre-clamp value was inside (the clamp passes the gradient)
 template <int P>
@@ -98,8 +64,8 @@ __device__ __forceinline__ uint32_t clamp_delta(float (&dd)[P][4], int variant) 
         for (int p = 0; p < P; ++p)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                if (!inside(dd[p][r], -20.0f, 20.0f)) bits &= ~(1u << (4 * p + r));
-                dd[p][r] = tclamp(dd[p][r], -20.0f, 20.0f);
+                if (!inside(dd[p][r], -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT)) bits &= ~(1u << (4 * p + r));
+                dd[p][r] = tclamp(dd[p][r], -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);
             }
     }
     return bits;
@@ -255,13 +221,7 @@ __device__ __forceinline__ void body(const BackwardArgs& a, float* __restrict__ 
             al[p] = hp[0]; ta[p] = hp[1]; rh[p] = hp[2]; et[p] = hp[3];
         }
         float gclip, vclip;
-        if (a.variant == 0) {
-            gclip = fmaxf(1.0f, 30.0f - (float)k);          // unfolded_DLASSO.py:80
-            vclip = fmaxf(10.0f, 200.0f - (float)(k * 3));  // unfolded_DLASSO.py:92
-        } else {
-            gclip = 10.0f;                                   // gnn_dlasso_models_progressive.py:212
-            vclip = 100.0f;                                  // :224, :232
-        }
+        iter_clips(a.variant, k, gclip, vclip);
         float part[P][4];
 #pragma unroll
         for (int p = 0; p < P; ++p)
@@ -307,7 +267,7 @@ __device__ __forceinline__ void body(const BackwardArgs& a, float* __restrict__ 
                 BWD_NEXT(0, cy1);
                 cons(t1, t2, mk);
                 const uint32_t md1 = clamp_delta(t2, a.variant);
-                fence();
+                compiler_fence();
                 // dual update adjoint (:98-99); t1 = d_bar
 #pragma unroll
                 for (int p = 0; p < P; ++p) {
@@ -333,7 +293,7 @@ __device__ __forceinline__ void body(const BackwardArgs& a, float* __restrict__ 
                 for (int p = 0; p < P; ++p)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) yb[p][BWD_ROW(4 * tt + r, r)] += t2[p][r];
-                fence();
+                compiler_fence();
                 // t1 = y_k; t2 = delta_k (k > 0: formed from y_k as the forward did; k = 0: d0)
                 if (k > 0) {
 #pragma unroll
@@ -354,7 +314,7 @@ __device__ __forceinline__ void body(const BackwardArgs& a, float* __restrict__ 
                     }
                 }
                 BWD_NEXT(3, cyk);
-                fence();
+                compiler_fence();
                 // primal update + gradient clamp adjoint (:73-93)
 #pragma unroll
                 for (int p = 0; p < P; ++p) {
@@ -421,7 +381,7 @@ __device__ __forceinline__ void body(const BackwardArgs& a, float* __restrict__ 
                         av[(t + 1) & 1][i] = bload4(rA, voffA + 64 * (t + 1),
                                                     (uint32_t)((HALF + AS * i) * MP * NP * 4));
                 }
-                fence();
+                compiler_fence();
 #pragma unroll
                 for (int i = 0; i < TH; ++i) {
                     const f32x4 bv = *(const f32x4*)(brow + (HALF + AS * i) * BT * YS + 16 * t);
@@ -452,7 +412,7 @@ __device__ __forceinline__ void body(const BackwardArgs& a, float* __restrict__ 
             for (int c = 0; c < NS; ++c) {
                 const int p = c / T2, tt = c % T2;
                 if (c + 1 < NS) load_at(tring[(c + 1) & 1], c + 1);
-                fence();
+                compiler_fence();
                 f32x4 rv[MP / 16];
 #pragma unroll
                 for (int t = 0; t < MP / 16; ++t)

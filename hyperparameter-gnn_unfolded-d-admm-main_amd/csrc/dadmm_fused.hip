@@ -32,6 +32,7 @@
 
 #include "dadmm_internal.h"
 #include "dadmm_consensus.h"
+#include "dadmm_device.h"
 
 #ifndef DADMM_FUSED_REC
 #define DADMM_FUSED_REC 0
@@ -52,86 +53,6 @@
 //     ds_read_b32 (b128 chunks removed the remaining bank conflicts but spilled: slower).
 
 namespace dadmm {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ rsrc_t make_rsrc(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ f32x4 bload4(rsrc_t r, uint32_t voff, uint32_t soff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
-typedef __attribute__((address_space(3))) void lds_void;
-// s_waitcnt vmcnt(n) for a small compile-time n (the switch folds once the loops are unrolled)
-__device__ __forceinline__ void wait_vm(int n) {
-    switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-        case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-        case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
-        case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-        case 13: asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); break;
-        case 14: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
-        case 15: asm volatile("s_waitcnt vmcnt(15)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;   // (over-waits: safe)
-    }
-}
-__device__ __forceinline__ void bstore4(f32x4 v, rsrc_t r, uint32_t voff, uint32_t soff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, v), r, voff, soff, 0);
-}
-// The iterate stream Y (K*B*P*n*4 bytes, 524 MB at the headline shape) is written once and never
-// re-read by the kernel; its cache policy decides whether it evicts the operator A / A^T that
-// every workgroup re-reads from L2 each iteration. aux: 16 = sc1, 2 = nt.
-__device__ __forceinline__ void bstore4_stream(f32x4 v, rsrc_t r, uint32_t voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, v), r, voff, 0, 16);
-}
-
-// torch.clamp(x, lo, hi) == min(max(x, lo), hi) for every non-NaN x. A NaN never needs to be
-// propagated here: the kernel flags (status bits) every case in which a NaN would reach one of the
-// reference's guards, and the caller then re-runs the batch through the guarded path.
-__device__ __forceinline__ float tclamp(float x, float lo, float hi) {
-    return fminf(fmaxf(x, lo), hi);
-}
-// torch.sign for float: (0 < x) - (x < 0)
-__device__ __forceinline__ float tsign(float x) { return (float)((0.0f < x) - (x < 0.0f)); }
-// tclamp as one v_med3_f32: equal to min(max(x, lo), hi) for every non-NaN x when lo <= hi
-// (-0 stays -0: the median of {lo, -0, hi}); NaN cases are flagged like tclamp's
-__device__ __forceinline__ float mclamp(float x, float lo, float hi) {
-    return __builtin_amdgcn_fmed3f(x, lo, hi);
-}
-// The hyper-parameter table through the scalar cache (s_load): it is read-only for the whole
-// launch, so a constant-address-space view lets the uniform per-iteration reads bypass the vector
-// memory queue (no vmcnt wait at the top of an iteration)
-typedef const __attribute__((address_space(4))) float cfloat;
-__device__ __forceinline__ bool finitef(float x) { return __builtin_isfinite(x); }
-
-// A per-iteration opaque copy of a loop-invariant offset: keeps `base + constant` inside the loop
-// so instruction selection folds the constant into the load's immediate offset instead of LICM
-// hoisting one register per constant out of the loop.
-__device__ __forceinline__ uint32_t fresh(uint32_t x) {
-    asm volatile("" : "=v"(x) : "0"(x));
-    return x;
-}
-
-__device__ __forceinline__ uint32_t fresh_s(uint32_t x) {   // same, for a wave-uniform value
-    asm volatile("" : "=s"(x) : "0"(x));
-    return x;
-}
-
 
 // The paired-chain GEMM2's A^T ring, simulated at compile time: quarter q = (4 p + t) T2 + tt is
 // A^T_p rows of n-tile tt, m-block t. PRE quarters are issued before the phase (under GEMM1's
@@ -160,9 +81,6 @@ struct G2Plan {
         }
     }
 };
-
-// Compiler-only memory barrier: bounds how far the scheduler hoists operand loads.
-__device__ __forceinline__ void compiler_fence() { asm volatile("" ::: "memory"); }
 
 // GRAPH: GRAPH_SHARED (one graph, ascending adjacency), GRAPH_LANE (per-sample, ascending),
 //        GRAPH_ORDERED (per-sample, explicit adjacency order).
@@ -361,7 +279,7 @@ __device__ __forceinline__ void fused_body(const FusedArgs& a, float* __restrict
 #pragma unroll
     for (int p = 0; p < P; ++p) et_prev[p] = 0.0f;
     // GNN variant: delta clamped to +-20 (:229); the unfolded variant: +-inf (a no-op on finite d)
-    const float dlim = a.variant != 0 ? 20.0f : __builtin_inff();
+    const float dlim = a.variant != 0 ? GNN_DELTA_LIMIT : __builtin_inff();
     auto dual_update_row = [&](int e, const uint32_t (&mk)[P], bool live, const float* yrow = nullptr) {
         float yy[P][1], dd[P][1];
 #pragma unroll
@@ -404,13 +322,7 @@ __device__ __forceinline__ void fused_body(const FusedArgs& a, float* __restrict
             al[p] = hp[0]; ta[p] = hp[1]; rh[p] = hp[2]; et[p] = hp[3];
         }
         float gclip, vclip;
-        if (a.variant == 0) {
-            gclip = fmaxf(1.0f, 30.0f - (float)k);          // unfolded_DLASSO.py:80
-            vclip = fmaxf(10.0f, 200.0f - (float)(k * 3));  // unfolded_DLASSO.py:92
-        } else {
-            gclip = 10.0f;                                   // gnn_dlasso_models_progressive.py:212
-            vclip = 100.0f;                                  // :224, :232
-        }
+        iter_clips(a.variant, k, gclip, vclip);
         const bool deferred = k > 0;
 
         // ---- GEMM1: R_p = A_p y_p - b_p for this wave's TH tiles, with the previous
@@ -499,11 +411,11 @@ __device__ __forceinline__ void fused_body(const FusedArgs& a, float* __restrict
                 }
                 *(f32x4*)(Ylds + (p * BT + j) * YS + n0) = yn;
                 // Y[k][s][p][n0..n0+3]; rows past n go to an offset the range check drops
-                bstore4_stream(yn, rY, n0 < n ? voffY + (uint32_t)((p * n + nb * 16) * 4) : 0x80000000u);
+                bstore4<16>(yn, rY, n0 < n ? voffY + (uint32_t)((p * n + nb * 16) * 4) : 0x80000000u);
                 if constexpr (REC) {
                     const uint32_t o = n0 < n ? voffY + (uint32_t)((p * n + nb * 16) * 4) : 0x80000000u;
-                    bstore4_stream(grv, rG, o);
-                    bstore4_stream(urv, rUr, o);
+                    bstore4<16>(grv, rG, o);
+                    bstore4<16>(urv, rUr, o);
                 }
             };
             // stores of one primal update (Y[k], and Grec / Urec when recording)
@@ -531,7 +443,7 @@ __device__ __forceinline__ void fused_body(const FusedArgs& a, float* __restrict
                     f32x4 av[T2];
 #pragma unroll
                     for (int tt = 0; tt < T2; ++tt) {
-                        wait_vm(plan.younger[q0 + tt]);
+                        wait_vm<16>(plan.younger[q0 + tt]);
                         av[tt] = *(const f32x4*)(Qlds + (w * QD + (q0 + tt) % QD) * 256 + lane * 4);
                     }
 #pragma unroll

@@ -33,12 +33,11 @@
 
 #include <type_traits>
 
+#include "dadmm_device.h"
 #include "dadmm_internal.h"
 
 namespace dadmm {
 namespace gnn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int THREADS = 256;   // 4 waves
 constexpr int WAVES = 4;
@@ -50,33 +49,6 @@ constexpr int WAVES = 4;
 // units) is loaded at once (round 5); the step adjoint's per-sample hyper-parameter sums run on
 // DPP moves and readlanes (wave_sum_dpp); update_item loads the guard flags and y_k's table entry
 // together; gram_kernel<true> serves grids of <= 2 items per CU at m_pad = 64, n_pad = 256.
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-// torch.clamp: NaN propagates, +-inf saturate
-__device__ __forceinline__ float clamp_t(float x, float lo, float hi) {
-    return x != x ? x : fminf(fmaxf(x, lo), hi);
-}
-__device__ __forceinline__ bool inside(float x, float lo, float hi) { return x >= lo && x <= hi; }
-__device__ __forceinline__ bool finitef(float x) { return __builtin_isfinite(x); }
-__device__ __forceinline__ int flag_ld(const int32_t* f) {
-    return __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void flag_or(int32_t* f, bool v) {
-    if (__ballot(v) != 0 && (threadIdx.x & 63) == 0)
-        __hip_atomic_fetch_or(f, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ void clips(const GnnArgs& a, int k, float& gclip, float& vclip) {
-    if (a.variant == 0) {
-        gclip = fmaxf(1.0f, 30.0f - (float)k);          // unfolded_DLASSO.py:80
-        vclip = fmaxf(10.0f, 200.0f - (float)(k * 3));  // unfolded_DLASSO.py:92
-    } else {
-        gclip = 10.0f;                                   // gnn_dlasso_models_progressive.py:212
-        vclip = 100.0f;                                  // :224, :232
-    }
-}
 
 // y_k as the reference holds it at the top of iteration k: y_{j+1} (yptr[j+1]) for the last
 // j < k whose y_next passed its guard, else y0 — read as zeros when the k = 0 guard fired
@@ -146,8 +118,7 @@ __global__ __launch_bounds__(THREADS) void gram_kernel(GnnArgs a, int k, const f
         const bool prev = walk_x && k >= 1;
         // the flag word through a descriptor whose range is empty when there is no k - 1 (reads 0,
         // touches nothing); flags written by earlier launches are visible at this launch's start
-        const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<int32_t*>(a.flags), 0, prev ? 4 * (GNN_F_YNB(k - 1) + 1) : 0, 0x00020000);
+        const rsrc_t rf = make_rsrc(a.flags, prev ? 4 * (GNN_F_YNB(k - 1) + 1) : 0);
         const int f_raw = __builtin_amdgcn_raw_buffer_load_b32(rf, prev ? 4 * GNN_F_YNB(k - 1) : 0, 0, 0);
         const float* y_prev = nullptr;
         if (prev) y_prev = a.yptr[k];
@@ -158,15 +129,14 @@ __global__ __launch_bounds__(THREADS) void gram_kernel(GnnArgs a, int k, const f
         for (int u = 0; u < T; ++u) ar[u] = *(const f32x4*)(arow + 16 * u);
         // GEMM2's units: n-tiles w, w + 4, w + 8, w + 12 (one m-group)
         const float* atb = a.At + ((size_t)p * 256 + j) * 64 + 4 * h;
-        const __amdgpu_buffer_rsrc_t ro =
-            __builtin_amdgcn_make_buffer_rsrc(out, 0, mode == 2 ? (int)((size_t)B * P * n * 4) : 0, 0x00020000);
+        const rsrc_t ro = make_rsrc(out, mode == 2 ? (uint32_t)((size_t)B * P * n * 4) : 0);
 #pragma unroll
         for (int u = 0; u < MB; ++u) {
 #pragma unroll
             for (int t = 0; t < 4; ++t) at_all[u][t] = *(const f32x4*)(atb + (size_t)16 * (w + WAVES * u) * 64 + 16 * t);
             const int n0 = 16 * (w + WAVES * u) + 4 * h;
             const uint32_t off = (sv && n0 < n) ? (uint32_t)((((size_t)s * P + p) * n + n0) * 4) : 0x80000000u;
-            oall[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ro, off, 0, 0));
+            oall[u] = bload4(ro, off);
         }
         __builtin_amdgcn_sched_barrier(0);
         bool zero = false;
@@ -180,14 +150,12 @@ __global__ __launch_bounds__(THREADS) void gram_kernel(GnnArgs a, int k, const f
             zero = __builtin_amdgcn_readfirstlane((int)zero) != 0;
         }
         const uint32_t xbytes = zero ? 0u : (uint32_t)((size_t)B * P * n * 4);
-        const __amdgpu_buffer_rsrc_t rx =
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xs), 0, (int)xbytes, 0x00020000);
+        const rsrc_t rx = make_rsrc(xs, xbytes);
         const uint32_t xoff = sv ? (uint32_t)((((size_t)s * P + p) * n + 4 * h) * 4) : 0x80000000u;
         f32x4 xr[T];
 #pragma unroll
         for (int u = 0; u < T; ++u)
-            xr[u] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                rx, 16 * u + 4 * h < n && sv ? xoff + 64u * u : 0x80000000u, 0, 0));
+            xr[u] = bload4(rx, 16 * u + 4 * h < n && sv ? xoff + 64u * u : 0x80000000u);
         __builtin_amdgcn_sched_barrier(0);
         f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
@@ -229,12 +197,10 @@ __global__ __launch_bounds__(THREADS) void gram_kernel(GnnArgs a, int k, const f
             if (16 * mq < m) {
                 const float* arow = a.A + ((size_t)p * MP + 16 * mq + j) * NP + 4 * h;
                 const uint32_t xbytes = zero ? 0u : (uint32_t)((size_t)B * P * n * 4);
-                const __amdgpu_buffer_rsrc_t rx =
-                    __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xs), 0, (int)xbytes, 0x00020000);
+                const rsrc_t rx = make_rsrc(xs, xbytes);
                 const uint32_t xoff = sv ? (uint32_t)((((size_t)s * P + p) * n + 4 * h) * 4) : 0x80000000u;
                 auto ldx = [&](int t) -> f32x4 {
-                    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                        rx, 16 * t + 4 * h < n && sv ? xoff + 64u * t : 0x80000000u, 0, 0));
+                    return bload4(rx, 16 * t + 4 * h < n && sv ? xoff + 64u * t : 0x80000000u);
                 };
                 const int T = NP / 16;
                 // ring depth 8 where the steps divide (round 5: half the exposed round trips of the
@@ -334,13 +300,12 @@ __global__ __launch_bounds__(THREADS) void gram_kernel(GnnArgs a, int k, const f
     f32x4 gc = {0.0f, 0.0f, 0.0f, 0.0f};
     // mode 2 (out += ...): the out rows of the unit that completes a tile are loaded one unit
     // ahead (a load issued just before its add left the HBM latency exposed once per tile)
-    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
-        out, 0, (mode == 2) ? (int)((size_t)B * P * n * 4) : 0, 0x00020000);
+    const rsrc_t ro = make_rsrc(out, mode == 2 ? (uint32_t)((size_t)B * P * n * 4) : 0);
     auto ldo = [&](int u) -> f32x4 {
         const int nb = w + WAVES * (u / MG), mg = u % MG, n0 = 16 * nb + 4 * h;
         const uint32_t off = (mg == MG - 1 && sv && n0 < n) ? (uint32_t)((((size_t)s * P + p) * n + n0) * 4)
                                                            : 0x80000000u;
-        return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ro, off, 0, 0));
+        return bload4(ro, off);
     };
     f32x4 ocur = {0.0f, 0.0f, 0.0f, 0.0f}, onxt = ocur;
     if (mode == 2 && units > 0) ocur = ldo(0);
@@ -421,13 +386,11 @@ __global__ __launch_bounds__(64 * GL_WAVES) void gram_lds_kernel(GnnArgs a, int 
     bool zero = false;
     const float* xs = x_raw != nullptr ? x_raw : y_source(a, k, zero);
     const uint32_t sbytes = (uint32_t)((size_t)B * P * n * 4);
-    const __amdgpu_buffer_rsrc_t rx =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xs), 0, zero ? 0 : (int)sbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(out, 0, (int)sbytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t roi = __builtin_amdgcn_make_buffer_rsrc(out, 0, mode == 2 ? (int)sbytes : 0, 0x00020000);
+    const rsrc_t rx = make_rsrc(xs, zero ? 0 : sbytes);
+    const rsrc_t ro = make_rsrc(out, sbytes);
+    const rsrc_t roi = make_rsrc(out, mode == 2 ? sbytes : 0);
     const bool has_add = mode == 2 && a.acc_add != nullptr;
-    const __amdgpu_buffer_rsrc_t rad =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.acc_add), 0, has_add ? (int)sbytes : 0, 0x00020000);
+    const rsrc_t rad = make_rsrc(a.acc_add, has_add ? sbytes : 0);
     __syncthreads();
 
     const int t_end = min(tiles, (grp + 1) * tpw);
@@ -441,7 +404,7 @@ __global__ __launch_bounds__(64 * GL_WAVES) void gram_lds_kernel(GnnArgs a, int 
         for (int g = 0; g < MQ; ++g) R[g] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
         auto ldx = [&](int t) -> f32x4 {
             const uint32_t off = (t < T && 16 * t + 4 * h < n && sv) ? rowoff + (uint32_t)(64 * t + 16 * h) : 0x80000000u;
-            return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0));
+            return bload4(rx, off);
         };
         auto lda = [&](f32x4 (&dst)[MQ], int t) {
 #pragma unroll
@@ -477,11 +440,11 @@ __global__ __launch_bounds__(64 * GL_WAVES) void gram_lds_kernel(GnnArgs a, int 
         };
         auto ldo = [&](int nb) -> f32x4 {
             const uint32_t off = (nb < NT && 16 * nb + 4 * h < n && sv) ? rowoff + (uint32_t)(64 * nb + 16 * h) : 0x80000000u;
-            return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(roi, off, 0, 0));
+            return bload4(roi, off);
         };
         auto ldd = [&](int nb) -> f32x4 {   // mode 2's addend rows (zeros when there is none)
             const uint32_t off = (nb < NT && 16 * nb + 4 * h < n && sv) ? rowoff + (uint32_t)(64 * nb + 16 * h) : 0x80000000u;
-            return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rad, off, 0, 0));
+            return bload4(rad, off);
         };
         // mode 2's out rows (and addend rows) two pairs ahead (oc: this pair, on: the next)
         f32x4 oc0 = ldo(0), oc1 = ldo(1), on0 = ldo(2), on1 = ldo(3);
@@ -507,8 +470,8 @@ __global__ __launch_bounds__(64 * GL_WAVES) void gram_lds_kernel(GnnArgs a, int 
             const uint32_t s0 = (16 * n0 + 4 * h < n && sv) ? rowoff + (uint32_t)(64 * n0 + 16 * h) : 0x80000000u;
             const uint32_t s1 = (n0 + 1 < NT && 16 * (n0 + 1) + 4 * h < n && sv)
                                     ? rowoff + (uint32_t)(64 * (n0 + 1) + 16 * h) : 0x80000000u;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) uint32_t, o0), ro, s0, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) uint32_t, o1), ro, s1, 0, 0);
+            bstore4(o0, ro, s0);
+            bstore4(o1, ro, s1);
             oc0 = on0;
             oc1 = on1;
             on0 = ldo(n0 + 4);
@@ -574,7 +537,7 @@ __device__ __forceinline__ void update_item(const GnnArgs& a, int k, int item, f
     const bool uzero = f_u != 0;
     float* const fix = (FUSED && k > 0 && f_prev != 0) ? y_prev : nullptr;
     float gclip, vclip;
-    clips(a, k, gclip, vclip);
+    iter_clips(a.variant, k, gclip, vclip);
     float* yl = lds;                                  // [P][UCB] y_{k+1}
     int32_t* vpl = (int32_t*)(yl + P * UCB);          // [P + 1] list starts (sample-local)
     uint8_t* vl = (uint8_t*)(vpl + P + 1);            // the sample's visit lists
@@ -701,7 +664,7 @@ __device__ __forceinline__ void update_item(const GnnArgs& a, int k, int item, f
             f32x4 un;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                if (a.variant != 0) acc[r] = clamp_t(acc[r], -20.0f, 20.0f);          // :229
+                if (a.variant != 0) acc[r] = clamp_t(acc[r], -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);          // :229
                 un[r] = clamp_t(uv[u][r] + acc[r] * et, -vclip, vclip);              // :231-232
                 bad_u |= !finitef(un[r]);
             }
@@ -792,7 +755,7 @@ __global__ __launch_bounds__(THREADS) void step_backward_kernel(GnnArgs a, int k
     uint8_t* vql = (uint8_t*)(vpl + P + 1);
     const int s = blockIdx.x;
     float gclip, vclip;
-    clips(a, k, gclip, vclip);
+    iter_clips(a.variant, k, gclip, vclip);
     const float* ys = a.yk;
     const int g0 = a.graph_shared ? 0 : s * P;
     for (int i = lane; i < 4 * H; i += 64) red[i] = 0.0f;
@@ -859,13 +822,13 @@ __global__ __launch_bounds__(THREADS) void step_backward_kernel(GnnArgs a, int k
                 float dbr = 0.0f, pe = 0.0f;
                 rwb[p] = 0.0f;
                 if (cv) {
-                    const float d1 = a.variant != 0 ? clamp_t(acc, -20.0f, 20.0f) : acc;
+                    const float d1 = a.variant != 0 ? clamp_t(acc, -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT) : acc;
                     const float et = hyp_at(a, s, 3, p);
                     const float wvv = rU[p] + d1 * et;
                     const float wb = (gg.gU1 != nullptr && inside(wvv, -vclip, vclip)) ? rgU1[p] : 0.0f;
                     pe = wb * d1;
                     const float db = (gg.gd1 != nullptr ? rgd1[p] : 0.0f) + wb * et;
-                    dbr = (a.variant == 0 || inside(acc, -20.0f, 20.0f)) ? db : 0.0f;
+                    dbr = (a.variant == 0 || inside(acc, -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT)) ? db : 0.0f;
                     rwb[p] = wb;
                 }
                 accum(3, p, pe);
@@ -942,13 +905,13 @@ __global__ __launch_bounds__(THREADS) void step_backward_kernel(GnnArgs a, int k
                 float dbr = 0.0f, pe = 0.0f;
                 if (cv) {
                     const size_t off = base + (size_t)p * n;
-                    const float d1 = a.variant != 0 ? clamp_t(acc, -20.0f, 20.0f) : acc;
+                    const float d1 = a.variant != 0 ? clamp_t(acc, -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT) : acc;
                     const float et = hyp_at(a, s, 3, p);
                     const float wvv = a.U[off] + d1 * et;
                     const float wb = (gg.gU1 != nullptr && inside(wvv, -vclip, vclip)) ? gg.gU1[off] : 0.0f;
                     pe = wb * d1;
                     const float db = (gg.gd1 != nullptr ? gg.gd1[off] : 0.0f) + wb * et;
-                    dbr = (a.variant == 0 || inside(acc, -20.0f, 20.0f)) ? db : 0.0f;
+                    dbr = (a.variant == 0 || inside(acc, -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT)) ? db : 0.0f;
                     gg.gU[off] = wb;
                 }
                 accum(3, p, pe);

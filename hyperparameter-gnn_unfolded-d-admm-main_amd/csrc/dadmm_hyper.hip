@@ -30,20 +30,16 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "dadmm_device.h"
 #include "dadmm_internal.h"
 
 namespace dadmm {
 namespace hyper {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int THREADS = 256;
 constexpr int TN = 64;            // output columns per workgroup (4 waves x 16)
 constexpr int ZS = TN + 4;        // LDS row stride of the GCN epilogue tile (float4 rows)
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 // scheduling barrier: pins where the ring's loads issue (between the steps' MFMAs)
 __device__ __forceinline__ void mem_fence() { __builtin_amdgcn_sched_barrier(0); }
 
@@ -54,48 +50,12 @@ __device__ __forceinline__ void mem_fence() { __builtin_amdgcn_sched_barrier(0);
 constexpr int HYPER_DMA_MIN = 32;  // k-steps per workgroup from which the DMA ring is used
 constexpr int HYPER_DQ = 4;
 constexpr int HYPER_D1 = 4;
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-typedef __attribute__((address_space(3))) void lds_void;
-__device__ __forceinline__ rsrc_t make_rsrc(const void* base, size_t bytes) {
-    const uint32_t nb = bytes > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (uint32_t)bytes;
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)nb, 0x00020000);
-}
 // one lane-linear 1 KB LDS-DMA: lane l's 16 bytes from voff land at lds + 16 l
 __device__ __forceinline__ void dma16(rsrc_t r, float* lds, uint32_t voff) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void*)lds, 16, voff, 0, 0, 0);
 }
-// s_waitcnt vmcnt(n) for a runtime n (the wait counts of the DMA ring depend on the wave)
-__device__ __forceinline__ void wait_vm(int n) {
-    switch (n) {
-        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-        case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-        case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
-        case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-        case 13: asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); break;
-        case 14: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(15)" ::: "memory"); break;
-    }
-}
 // this wave's LDS reads done, then the workgroup barrier (no vmcnt drain: DMAs stay in flight)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// XCD-aware tile order: the dispatcher deals blocks round-robin over the 8 XCDs (each with its
-// own L2); consecutive tile numbers — the column tiles of one row tile, which read the same input
-// rows — are given to blocks of one XCD.
-__device__ __forceinline__ int xcd_tile(int bid, int G) {
-    constexpr int NX = 8;
-    const int xcd = bid % NX, i = bid / NX, q = G / NX, r = G % NX;
-    return xcd < r ? xcd * (q + 1) + i : r * (q + 1) + (xcd - r) * q + i;
-}
 
 // Workgroup tile: 32 WR rows x 64 columns, 4 waves in a 2 x 2 layout; wave (wr, wc) owns row
 // blocks wr WR .. wr WR + WR - 1 and column blocks 2 wc, 2 wc + 1 (16 x 16 each, WR x 2 MFMA
@@ -122,7 +82,7 @@ __global__ __launch_bounds__(THREADS * KS) void linear_kernel(HyperArgs a) {
     const int wr = wq >> 1, wcol = wq & 1;
 
     const int gm = a.gm, gn = a.gn;
-    const int tl = xcd_tile(blockIdx.x, gridDim.x);
+    const int tl = xcd_swizzle(blockIdx.x, gridDim.x);
     const int ct = tl % gn, rt = (tl / gn) % gm, split = tl / (gn * gm);
 
     constexpr bool GCN = EPI == HYPER_EPI_GCN || EPI == HYPER_EPI_GCN_TRAIN || EPI == HYPER_EPI_GCN_BWD;
@@ -241,9 +201,9 @@ __global__ __launch_bounds__(THREADS * KS) void linear_kernel(HyperArgs a) {
         const int epi = TM * ZS + ((a.S_t * a.P * a.P + 3) & ~3) + 4 * TN;
         pf = zt + (RING > epi ? RING : epi);
         float* pst = pf + TM * TN;                                   // mean [SR][64], var [SR][64]
-        const rsrc_t rm = make_rsrc(a.save_m, (size_t)a.B * a.P * a.N * 4);
-        const rsrc_t rmu = make_rsrc(a.save_mean, (size_t)a.B * a.N * 4);
-        const rsrc_t rva = make_rsrc(a.save_var, (size_t)a.B * a.N * 4);
+        const rsrc_t rm = make_rsrc_sat(a.save_m, (size_t)a.B * a.P * a.N * 4);
+        const rsrc_t rmu = make_rsrc_sat(a.save_mean, (size_t)a.B * a.N * 4);
+        const rsrc_t rva = make_rsrc_sat(a.save_var, (size_t)a.B * a.N * 4);
         const int rr = lane >> 4, c4 = 4 * (lane & 15);   // lane-linear: 4 rows x 64 columns per copy
         for (int q = w; 4 * q < rows_t; q += 4 * KS)
             dma16(rm, pf + q * 256, (uint32_t)(((size_t)(row0 + 4 * q + rr) * a.N + col0 + c4) * 4));
@@ -263,9 +223,9 @@ __global__ __launch_bounds__(THREADS * KS) void linear_kernel(HyperArgs a) {
         const int nbw = NB % 4 == 0 ? NB / 4 : (NB - wu + 3) / 4;   // blocks this wave copies per k-step
         const int T = t_end - t_begin, t1 = SPLIT ? K1 / 16 : KF;
         const int kq = 4 * (lane >> 4);
-        const rsrc_t rx1 = make_rsrc(a.x1 + (size_t)row0 * a.ld1, (size_t)rows_t * a.ld1 * 4);
-        const rsrc_t rx2 = make_rsrc(SPLIT ? a.x2 + (size_t)row0 * a.ld2 : a.x1, SPLIT ? (size_t)rows_t * a.ld2 * 4 : 0);
-        const rsrc_t rw = make_rsrc(a.W, (size_t)a.N * a.ldw * 4);
+        const rsrc_t rx1 = make_rsrc_sat(a.x1 + (size_t)row0 * a.ld1, (size_t)rows_t * a.ld1 * 4);
+        const rsrc_t rx2 = make_rsrc_sat(SPLIT ? a.x2 + (size_t)row0 * a.ld2 : a.x1, SPLIT ? (size_t)rows_t * a.ld2 * 4 : 0);
+        const rsrc_t rw = make_rsrc_sat(a.W, (size_t)a.N * a.ldw * 4);
         uint32_t o1[NBW], o2[NBW];
 #pragma unroll
         for (int i = 0; i < NBW; ++i) {
@@ -313,7 +273,7 @@ __global__ __launch_bounds__(THREADS * KS) void linear_kernel(HyperArgs a) {
         auto body = [&](int u, f32x4 (&fa)[WR], f32x4 (&fb)[2], f32x4 (&na)[WR], f32x4 (&nb)[2]) {
             int younger = DQ - 2 < T - 2 - u ? DQ - 2 : T - 2 - u;
             younger = younger > 0 ? younger : 0;
-            wait_vm(nbw * younger);
+            wait_vm<15>(nbw * younger);
             lds_barrier();
             if (u + DQ < T) dma(t_begin + u + DQ);
 #pragma unroll
@@ -333,7 +293,7 @@ __global__ __launch_bounds__(THREADS * KS) void linear_kernel(HyperArgs a) {
         if (T > 0) {
             const int pre = T < DQ ? T : DQ;
             for (int u = 0; u < pre; ++u) dma(t_begin + u);
-            wait_vm(nbw * (pre - 1));
+            wait_vm<15>(nbw * (pre - 1));
             lds_barrier();
             f32x4 fa0[WR], fb0[2], fa1[WR], fb1[2];
             frag(fa0, fb0, t_begin);
@@ -708,18 +668,13 @@ __host__ __device__ constexpr size_t g32_lds_bytes(int S_t, int P) {
     const size_t epi = 4 * ((size_t)G32_TM * ZS + 4 * TN);
     return ring > epi ? ring : epi;
 }
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
 __global__ __launch_bounds__(64 * G32_WAVES) void gcn32_kernel(HyperArgs a) {
     extern __shared__ __attribute__((aligned(16))) float zt[];
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wr = w >> 1, wc = w & 1;
     const int gn = a.gn;
-    const int tl = xcd_tile(blockIdx.x, gridDim.x);
+    const int tl = xcd_swizzle(blockIdx.x, gridDim.x);
     const int ct = tl % gn, rt = tl / gn;
     const int P = a.P;
     const int s0 = rt * a.S_t;
@@ -729,8 +684,8 @@ __global__ __launch_bounds__(64 * G32_WAVES) void gcn32_kernel(HyperArgs a) {
     const int K = a.K, T = (K + 15) / 16;
 
     // LDS-DMA sources: wave w copies A pieces 2w, 2w + 1 (16 rows each) and, for w < 4, W piece w
-    const rsrc_t rx = make_rsrc(a.x1 + (size_t)row0 * a.ld1, (size_t)rows_t * a.ld1 * 4);
-    const rsrc_t rw = make_rsrc(a.W, (size_t)a.N * a.ldw * 4);
+    const rsrc_t rx = make_rsrc_sat(a.x1 + (size_t)row0 * a.ld1, (size_t)rows_t * a.ld1 * 4);
+    const rsrc_t rw = make_rsrc_sat(a.W, (size_t)a.N * a.ldw * 4);
     const int pos = lane & 3;
     uint32_t oa[2], ka[2], ow = 0, kw = 0;
 #pragma unroll
@@ -792,7 +747,7 @@ __global__ __launch_bounds__(64 * G32_WAVES) void gcn32_kernel(HyperArgs a) {
     if (T > 0) {
         const int pre = T < G32_DQ ? T : G32_DQ;
         for (int u = 0; u < pre; ++u) dma(u);
-        wait_vm(nper * (pre - 1));
+        wait_vm<15>(nper * (pre - 1));
         lds_barrier();
         Frag f0, f1;
         frag(f0, 0, 0);
@@ -803,7 +758,7 @@ __global__ __launch_bounds__(64 * G32_WAVES) void gcn32_kernel(HyperArgs a) {
             mma(f0);
             int younger = G32_DQ - 2 < T - 2 - u ? G32_DQ - 2 : T - 2 - u;
             younger = younger > 0 ? younger : 0;
-            wait_vm(nper * younger);
+            wait_vm<15>(nper * younger);
             lds_barrier();
             if (u + G32_DQ < T) dma(u + G32_DQ);
             if (u + 1 < T) frag(f0, u + 1, 0);

@@ -19,25 +19,13 @@
 
 #include <type_traits>
 
+#include "dadmm_device.h"
 #include "dadmm_internal.h"
 
 namespace dadmm {
 namespace hgrad {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int THREADS = 256;
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-// XCD-aware order: consecutive tiles (the k-tiles of one n-tile, which read the same dZ columns)
-// on blocks of one XCD (the dispatcher deals blocks round-robin over the 8 XCDs)
-__device__ __forceinline__ int xcd_tile(int bid, int G) {
-    constexpr int NX = 8;
-    const int xcd = bid % NX, i = bid / NX, q = G / NX, r = G % NX;
-    return xcd < r ? xcd * (q + 1) + i : r * (q + 1) + (xcd - r) * q + i;
-}
 
 // ---- wgrad on 32x32x2 MFMA with coalesced row operands (round 4, the default) -------------------
 // The round-3 wgrad_kernel (16x16x4 MFMA, lanes loading one float of 16-column segments, 32 x 32
@@ -50,17 +38,12 @@ __device__ __forceinline__ int xcd_tile(int bid, int G) {
 // in split order by reduce_kernel: deterministic); the four waves' partials add through LDS in a
 // fixed tree. The bias column sums come from the same dZ reads (k-tile 0).
 constexpr int W2_T = 64, W2_WAVES = 4, W2_RING = 8;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
 __global__ __launch_bounds__(64 * W2_WAVES) void wgrad2_kernel(WgradArgs a) {
     __shared__ float red[2][4 * 16 + 1][64];          // two waves' partial tiles (+ bias) per tree level
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int i = lane & 31, kh = lane >> 5;
     const int gn = (a.N + W2_T - 1) / W2_T, gk = (a.K + W2_T - 1) / W2_T;
-    const int tl = xcd_tile(blockIdx.x, gridDim.x);
+    const int tl = xcd_swizzle(blockIdx.x, gridDim.x);
     const int kt = tl % gk, nt = (tl / gk) % gn, split = tl / (gk * gn);
     const int n0 = nt * W2_T, k0 = kt * W2_T;
     // rows in full pairs; an odd R leaves each block's last row to the tail below

@@ -20,19 +20,15 @@
 
 #include <type_traits>
 
+#include "dadmm_device.h"
 #include "dadmm_internal.h"
 
 namespace dadmm {
 namespace tail {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int RT = 16;                     // samples per workgroup
 constexpr int WAVES = 8;
 constexpr int THREADS = 64 * WAVES;
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 // out[16][N] (LDS, row stride ldo) = X[16][K] (LDS, row stride ldx) W^T, W [N][K] (row stride K):
 // the column blocks of 16 dealt to the waves; W loaded whole per block (K <= 16 WALL) or through a

@@ -24,12 +24,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dadmm_device.h"
 #include "dadmm_internal.h"
 
 namespace dadmm {
 namespace hyper_train {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int THREADS = 256;
 constexpr int CB = 64;   // columns per gcn_bwd workgroup
 // gcn_bwd workgroup size NT: its passes 1-2 use one lane per column (64), so at 256 threads three

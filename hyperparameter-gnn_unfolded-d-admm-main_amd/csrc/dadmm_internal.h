@@ -1,52 +1,11 @@
-// dadmm_internal.h — shared between the kernel translation units and the C-ABI layer.
+// dadmm_internal.h — shared between the kernel translation units and the C-ABI layer: argument
+// structs, launcher declarations, constants, drop_hash. (Device-only primitives: dadmm_device.h.)
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace dadmm {
-
-// Sum of v over the wave's 64 lanes, in a fixed order, on DPP moves (quad perms, half-row and row
-// mirrors: every lane ends with its 16-lane row's sum) and four readlanes: no LDS round trips (a
-// __shfl_xor butterfly is six ds_bpermute round trips). Deterministic; the association differs
-// from the butterfly's (f32 rounding). Uniform result.
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov_f32(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float wave_sum_dpp(float v) {
-    v = v + dpp_mov_f32<0xB1>(v);    // quad_perm [1,0,3,2]
-    v = v + dpp_mov_f32<0x4E>(v);    // quad_perm [2,3,0,1]: every lane holds its quad's sum
-    v = v + dpp_mov_f32<0x141>(v);   // row_half_mirror: its 8-lane group's
-    v = v + dpp_mov_f32<0x140>(v);   // row_mirror: its 16-lane row's
-    const auto lane_v = [&](int l) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
-    };
-    return (lane_v(0) + lane_v(16)) + (lane_v(32) + lane_v(48));
-}
-// Sum of v over each 16-lane row, in every lane of the row (the first four steps above).
-__device__ __forceinline__ float row16_sum_dpp(float v) {
-    v = v + dpp_mov_f32<0xB1>(v);
-    v = v + dpp_mov_f32<0x4E>(v);
-    v = v + dpp_mov_f32<0x141>(v);
-    return v + dpp_mov_f32<0x140>(v);
-}
-
-// The LayerNorm row sums (rownorm forward / backward and the hypernetwork tail kernel's copies of
-// them, which must reduce identically): wave_sum_dpp.
-__device__ __forceinline__ float ln_row_sum(float v) {
-    return wave_sum_dpp(v);
-}
-
-
-// sign(y) * t exactly as torch's eager ops give it (sign(+-0) = sign(NaN) = 0, so +0 there, else
-// +-t), without branches: the sign bit of y moved onto t, then one select. (The nested-ternary
-// form compiles to divergent branches, ~11 instructions per element in the middle of the MFMA
-// chains.)
-__device__ __forceinline__ float sign_times(float y, float t) {
-    const float st = __uint_as_float(__float_as_uint(t) ^ (__float_as_uint(y) & 0x80000000u));
-    return __builtin_fabsf(y) > 0.0f ? st : 0.0f;
-}
 
 constexpr int BT = 16;       // samples per workgroup of the fused kernel (MFMA N dimension)
 constexpr int M_PAD = 64;    // rows per m-group (4 m-blocks of 16 rows); the fused kernels hold one

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dadmm_device.h"
 #include "dadmm_internal.h"
 
 namespace dadmm {
@@ -19,10 +20,6 @@ namespace loss {
 
 constexpr int THREADS = 256;
 constexpr int CHUNK = 4096;   // granules (float4 or float) of one layer per workgroup
-
-__device__ __forceinline__ bool finitef(float x) { return __builtin_isfinite(x); }
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // partial[k][c] = sum of (Y - label)^2 over chunk c of layer k; flags |= 1 on a non-finite Y/label.
 // V = 4: float4 granules (n % 4 == 0 and n_store % 4 == 0), else V = 1. 32-bit index arithmetic

@@ -40,15 +40,12 @@
 
 #include "dadmm_internal.h"
 #include "dadmm_consensus.h"
+#include "dadmm_device.h"
 
 namespace dadmm {
 namespace split {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
 typedef __attribute__((address_space(1))) uint32_t gu32;
-typedef const __attribute__((address_space(4))) float cfloat;
 
 constexpr int NS = SPLIT_COLS;          // columns (rows of y) per slice
 constexpr int WV = 8;                   // waves per workgroup (2 per SIMD)
@@ -59,26 +56,6 @@ constexpr int WV = 8;                   // waves per workgroup (2 per SIMD)
 constexpr int AST = NS + 4;
 constexpr int YS = NS + 8;              // Ylds / Rlds: b128 reads conflict-free at 8 mod 64
 constexpr int RS = M_PAD + 8;
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ rsrc_t make_rsrc(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-// aux: 16 = sc1 (write-through store / L1-bypassing load)
-template <int AUX>
-__device__ __forceinline__ f32x4 bload4(rsrc_t r, uint32_t voff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, AUX));
-}
-template <int AUX>
-__device__ __forceinline__ void bstore4(f32x4 v, rsrc_t r, uint32_t voff) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, v), r, voff, 0, AUX);
-}
-__device__ __forceinline__ float mclamp(float x, float lo, float hi) {
-    return __builtin_amdgcn_fmed3f(x, lo, hi);
-}
-__device__ __forceinline__ bool finitef(float x) { return __builtin_isfinite(x); }
 
 // Wait until the epoch words of every other slice of the wave's TH (agent, m-block) tiles reach
 // `epoch`: lane t * S + s polls word s of tile t (sc1 loads; tile t's S words at words[t]), lanes
@@ -160,7 +137,7 @@ __device__ __forceinline__ void split_body(const SplitArgs& sa, float* __restric
         for (int i = threadIdx.x; i < nh; i += WV * 64) bad_h |= !finitef(a.hyp[i]);
         status |= bad_h ? 8u : 0u;
     }
-    const float dlim = a.variant != 0 ? 20.0f : __builtin_inff();
+    const float dlim = a.variant != 0 ? GNN_DELTA_LIMIT : __builtin_inff();
 
     int round = 0;
     for (int tile = g; tile < sa.tiles; tile += G, ++round) {
@@ -240,13 +217,7 @@ __device__ __forceinline__ void split_body(const SplitArgs& sa, float* __restric
                 al[i] = hp[0]; ta[i] = hp[1]; rh[i] = hp[2]; et[i] = hp[3];
             }
             float gclip, vclip;
-            if (a.variant == 0) {
-                gclip = fmaxf(1.0f, 30.0f - (float)k);          // unfolded_DLASSO.py:80
-                vclip = fmaxf(10.0f, 200.0f - (float)(k * 3));  // :92
-            } else {
-                gclip = 10.0f;                                   // gnn_dlasso_models_progressive.py:212
-                vclip = 100.0f;                                  // :224, :232
-            }
+            iter_clips(a.variant, k, gclip, vclip);
 
             // ---- GEMM1 partials c_s = A_p[:, slice] y_p[slice] (+ -b in slice 0), published one
             //      chain at a time: stored write-through (sc1); chain i-1's epoch word after chain

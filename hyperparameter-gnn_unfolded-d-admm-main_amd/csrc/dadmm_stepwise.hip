@@ -29,12 +29,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dadmm_device.h"
 #include "dadmm_internal.h"
 
 namespace dadmm {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SW_THREADS = 256;   // 4 waves
 constexpr int SW_WAVES = 4;
@@ -42,24 +41,6 @@ constexpr int SW_WAVES = 4;
 // 4 KB; longer lists are read from global memory (P > 45 with dense graphs)
 __host__ __device__ constexpr int sw_vcap(int P) {
     return ((2 * P * P < 4096 ? 2 * P * P : 4096) + 3) & ~3;
-}
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-// torch.clamp: NaN propagates, +-inf saturate
-__device__ __forceinline__ float clamp_t(float x, float lo, float hi) {
-    return x != x ? x : fminf(fmaxf(x, lo), hi);
-}
-__device__ __forceinline__ bool finitef(float x) { return __builtin_isfinite(x); }
-
-__device__ __forceinline__ int flag_ld(const int32_t* f) {
-    return __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// one atomic per wave (called with every lane of the wave active)
-__device__ __forceinline__ void flag_or(int32_t* f, bool v) {
-    if (__ballot(v) != 0 && (threadIdx.x & 63) == 0)
-        __hip_atomic_fetch_or(f, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // iteration k's y_k: Y[j] for the last j < k whose y_next passed the guard, else y0 (zeros when
@@ -79,16 +60,6 @@ __device__ __forceinline__ void hyp_row(const StepArgs& a, int k, int p, float& 
                                         float& rh, float& et) {
     const float* h = a.hyp + ((size_t)k * a.hyp_rows + (a.hyp_rows == 1 ? 0 : p)) * 4;
     al = h[0]; ta = h[1]; rh = h[2]; et = h[3];
-}
-
-__device__ __forceinline__ void clips(const StepArgs& a, int k, float& gclip, float& vclip) {
-    if (a.variant == 0) {
-        gclip = fmaxf(1.0f, 30.0f - (float)k);          // unfolded_DLASSO.py:80
-        vclip = fmaxf(10.0f, 200.0f - (float)(k * 3));  // unfolded_DLASSO.py:92
-    } else {
-        gclip = 10.0f;                                   // gnn_dlasso_models_progressive.py:212
-        vclip = 100.0f;                                  // :224, :232
-    }
 }
 
 // ---- phase 0: the k = 0 guards on y0 / U0 (:55-61), grid-stride over float4s -------------------
@@ -166,7 +137,7 @@ __device__ void phase_grad(const StepArgs& a, int k, int item, float* lds) {
     // GEMM2 + gradient assembly (:73-81): wave w takes n-tiles w, w + 4, ...
     float al, ta, rh, et, gclip, vclip;
     hyp_row(a, k, p, al, ta, rh, et);
-    clips(a, k, gclip, vclip);
+    iter_clips(a.variant, k, gclip, vclip);
     const float dg = sv ? a.deg[(a.graph_shared ? 0 : (size_t)s * P) + p] : 0.0f;
     bool bad = false;
     for (int nb = w; nb < NP / 16; nb += SW_WAVES) {
@@ -223,7 +194,7 @@ __device__ void phase_update(const StepArgs& a, int k, int item, float* ylds) {
     const bool uzero = flag_ld(a.flags + SW_F_UBAD(k)) != 0;
     const float* usrc = k == 0 ? a.U0 : a.U;
     float gclip, vclip;
-    clips(a, k, gclip, vclip);
+    iter_clips(a.variant, k, gclip, vclip);
     float* yl = ylds + (threadIdx.x >> 6) * (P * 64);   // this wave's [P][64] y_next
     const int lane = threadIdx.x & 63;
     // this wave's copy of the sample's visit lists: starts [P + 1] (relative), entries (bytes)
@@ -268,7 +239,7 @@ __device__ void phase_update(const StepArgs& a, int k, int item, float* ylds) {
             const uint8_t* __restrict__ vg = a.vq + v0;
             for (int t = vpl[p]; t < t1; ++t) acc = acc + (yp - yl[(int)vg[t] * 64 + lane]);
         }
-        if (a.variant != 0) acc = clamp_t(acc, -20.0f, 20.0f);             // GNN :229
+        if (a.variant != 0) acc = clamp_t(acc, -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);             // GNN :229
         if (cv) {
             const size_t off = base + (size_t)p * n;
             const float u = uzero ? 0.0f : usrc[off];

@@ -36,14 +36,11 @@
 
 #include <type_traits>
 
+#include "dadmm_device.h"
 #include "dadmm_internal.h"
 
 namespace dadmm {
 namespace stream {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-typedef __attribute__((address_space(3))) void lds_void;
 
 constexpr int NW = 8;            // waves per workgroup (the default form; 16: one agent per wave)
 constexpr int CT = 2;            // 16-column MFMA tiles per step
@@ -62,10 +59,6 @@ constexpr int SLOTS = 3;         // y-block ring: the block of step bs + 2 is lo
 #define DADMM_STR_(x) #x
 #define DADMM_STR(x) DADMM_STR_(x)
 
-__device__ __forceinline__ rsrc_t make_rsrc(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // A raw buffer descriptor as four SGPRs (for inline asm): base, stride 0, num_records = bytes,
@@ -92,25 +85,6 @@ __device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {
     asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float tclamp(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
-__device__ __forceinline__ bool finitef(float x) { return __builtin_isfinite(x); }
-__device__ __forceinline__ bool finite4(f32x4 v) {
-    return finitef(v[0]) && finitef(v[1]) && finitef(v[2]) && finitef(v[3]);
-}
-
-__device__ __forceinline__ void clips(int variant, int k, float& gclip, float& vclip) {
-    if (variant == 0) {
-        gclip = fmaxf(1.0f, 30.0f - (float)k);          // unfolded_DLASSO.py:80
-        vclip = fmaxf(10.0f, 200.0f - (float)(k * 3));  // unfolded_DLASSO.py:92
-    } else {
-        gclip = 10.0f;                                   // gnn_dlasso_models_progressive.py:212
-        vclip = 100.0f;                                  // :224, :232
-    }
-}
-
 // Visit-table row length: an agent's list holds <= 2 P entries (each neighbour from both ends of
 // the edge, a self-loop twice). Rows are padded with the agent itself (a term y_p - y_p = +0,
 // which leaves the accumulator unchanged: it starts at +0 and is never -0) to a multiple of 4
@@ -250,10 +224,8 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
                     dA, voa, sba + (uint32_t)((16 * t + r4) * NP * 4), 0));   // row step in soffset
         const uint32_t off = (pin && col_ok(c0, ct)) ? (uint32_t)(elem(pc, c0, ct) * 4) : 0x80000000u;
         // U_{k-1} (k = 0: U0 itself; k = 1: U_0 = U0)
-        r.u = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-            make_rsrc(k <= 1 ? a.U0 : a.Ubuf[0], s_bytes), k >= 0 ? off : 0x80000000u, 0, 0));
-        r.d = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(dd0, k == 0 ? off : 0x80000000u, 0,
-                                                                              0));
+        r.u = bload4(make_rsrc(k <= 1 ? a.U0 : a.Ubuf[0], s_bytes), k >= 0 ? off : 0x80000000u);
+        r.d = bload4(dd0, k == 0 ? off : 0x80000000u);
     };
     auto fetch_m = [&](int k, int c0, int i, Ring& r) {
         const int ai = i / CT, ct = i % CT;
@@ -263,9 +235,8 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
         const bool ok = k < K - 1 && pin;
 #pragma unroll
         for (int t = 0; t < 4; ++t)
-            r.am[t] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                dA, ok ? vam + (uint32_t)(16 * t * NP * 4) : 0x80000000u,
-                (uint32_t)((((size_t)pc * 64) * NP + c0 + 16 * ct) * 4), 0));
+            r.am[t] = bload4(dA, ok ? vam + (uint32_t)(16 * t * NP * 4) : 0x80000000u,
+                             (uint32_t)((((size_t)pc * 64) * NP + c0 + 16 * ct) * 4));
     };
 
     f32x4 Rk[PW][4], Rn[PW][4];
@@ -334,7 +305,7 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
         f32x4 dv = k == 0 ? r.d : acc;
         if (k >= 1 && a.variant != 0) {
 #pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) dv[r4] = tclamp(dv[r4], -20.0f, 20.0f);   // :229
+            for (int r4 = 0; r4 < 4; ++r4) dv[r4] = tclamp(dv[r4], -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);   // :229
         }
         // the dual update of iteration k - 1 (:98-99), deferred to here (k = 0: U0 as given)
         f32x4 uv;
@@ -346,9 +317,7 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
         bad_u0 |= k == 0 && okc && !finite4(uv);
         // U_k after the next tile's A rows are issued: vector-memory operations complete in order,
         // so a load issued after a store waits for it
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) uint32_t, uv),
-                                               make_rsrc(k == K ? a.U_out : a.Ubuf[0], s_bytes),
-                                               k >= 1 ? soff : 0x80000000u, 0, 0);
+        bstore4(uv, make_rsrc(k == K ? a.U_out : a.Ubuf[0], s_bytes), k >= 1 ? soff : 0x80000000u);
         const bool upd = k >= 0 && k < K;
         f32x4 yn, grc;
 #pragma unroll
@@ -364,15 +333,11 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
             bad_y |= upd && okc && !finitef(v);
             yn[r4] = okc ? v : 0.0f;
         }
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) uint32_t, yn),
-                                               make_rsrc(a.Y + (size_t)(upd ? k : 0) * S, s_bytes),
-                                               upd ? soff : 0x80000000u, 0, 0);
+        bstore4(yn, make_rsrc(a.Y + (size_t)(upd ? k : 0) * S, s_bytes), upd ? soff : 0x80000000u);
         if constexpr (REC) {   // the adjoint's trajectory: Grec[k] (pre-clamp gradient), Urec[k] = U_k
             const size_t kS = (size_t)(upd ? k : 0) * S;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) uint32_t, grc),
-                                                   make_rsrc(a.Grec + kS, s_bytes), upd ? soff : 0x80000000u, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) uint32_t, uv),
-                                                   make_rsrc(a.Urec + kS, s_bytes), upd ? soff : 0x80000000u, 0, 0);
+            bstore4(grc, make_rsrc(a.Grec + kS, s_bytes), upd ? soff : 0x80000000u);
+            bstore4(uv, make_rsrc(a.Urec + kS, s_bytes), upd ? soff : 0x80000000u);
         }
         bad_y0 |= k == -1 && okc && !finite4(yo);   // the :55 guard on y_0
         // GEMM1: R_{k+1} += A_p[:, tile] y_{k+1}[tile] (phase -1: R_0 from y_0)
@@ -401,8 +366,8 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
         // phase setup: hyper-parameters, clips, R_k <- R_{k+1}, the GEMM1 chains from -b
         const int kc = k < 0 ? 0 : (k < K ? k : K - 1), kp = k < 1 ? 0 : k - 1;
         float gtmp;
-        clips(a.variant, kc, gclip, vclip);
-        clips(a.variant, kp, gtmp, vclip_prev);
+        iter_clips(a.variant, kc, gclip, vclip);
+        iter_clips(a.variant, kp, gtmp, vclip_prev);
 #pragma unroll
         for (int ai = 0; ai < PW; ++ai) {
             const int p = w + NW * ai;

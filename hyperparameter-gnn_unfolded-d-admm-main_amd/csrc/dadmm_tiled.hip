@@ -25,39 +25,14 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "dadmm_device.h"
 #include "dadmm_internal.h"
 
 namespace dadmm {
 namespace tiled {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-
-__device__ __forceinline__ rsrc_t make_rsrc(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ f32x4 bload4(rsrc_t r, uint32_t voff) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, 0));
-}
-
 constexpr int THREADS = 256;   // 4 waves: GEMM1 = one 16-row m-block per wave
 constexpr int WAVES = 4;
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float tclamp(float x, float lo, float hi) { return fminf(fmaxf(x, lo), hi); }
-__device__ __forceinline__ bool finitef(float x) { return __builtin_isfinite(x); }
-
-__device__ __forceinline__ void clips(int variant, int k, float& gclip, float& vclip) {
-    if (variant == 0) {
-        gclip = fmaxf(1.0f, 30.0f - (float)k);          // unfolded_DLASSO.py:80
-        vclip = fmaxf(10.0f, 200.0f - (float)(k * 3));  // unfolded_DLASSO.py:92
-    } else {
-        gclip = 10.0f;                                   // gnn_dlasso_models_progressive.py:212
-        vclip = 100.0f;                                  // :224, :232
-    }
-}
 
 constexpr int HALVES = 2;            // 16-sample MFMA column blocks per workgroup (32 samples):
                                      // every A / A^T operand load feeds two fma chains
@@ -75,17 +50,6 @@ struct Chunk {                       // one chunk's operands
     f32x4 yp[RG], up[RG], dv[RG];
     f32x4 atv[CH][4 * MB];
 };
-
-// blockIdx -> (tile, agent) so that the P workgroups of one sample tile run on the same XCD
-// (dispatch is round-robin over the 8 XCDs, each with its own L2): the neighbour tiles a
-// workgroup reads for delta are its siblings' own tiles, hot in that L2.
-__device__ __forceinline__ int xcd_swizzle(int bid, int G) {
-    constexpr int NX = 8;
-    const int xcd = bid % NX, i = bid / NX, q = G / NX, r = G % NX;
-    return xcd < r ? xcd * (q + 1) + i : r * (q + 1) + (xcd - r) * q + i;
-}
-
-typedef __attribute__((address_space(3))) void lds_void;
 
 // STAGE (n_pad <= STAGE_NP_MAX): the workgroup's y_k tile [ST][n_pad] is copied HBM -> LDS by
 // buffer_load ... lds (no VGPRs, the whole 64 KB in flight at once) at the start of the
@@ -298,12 +262,12 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(2))) vo
         const float* hk = a.hyp + ((size_t)k * H + hp) * 4;
         al = hk[0]; ta = hk[1]; rh = hk[2]; et = hk[3];
         status |= (finitef(al) && finitef(ta) && finitef(rh) && finitef(et)) ? 0u : 8u;
-        clips(a.variant, k, gclip, vclip);
+        iter_clips(a.variant, k, gclip, vclip);
     }
     if (k > 0) {
         et_prev = a.hyp[((size_t)(k - 1) * H + hp) * 4 + 3];
         float gtmp;
-        clips(a.variant, k - 1, gtmp, vclip_prev);
+        iter_clips(a.variant, k - 1, gtmp, vclip_prev);
     }
     float* Ucur = final_only ? a.U_out : a.Ubuf[k & 1];   // U_k
 
@@ -350,7 +314,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(2))) vo
             } else {
                 if (a.variant != 0) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) c.dv[g][r] = tclamp(c.dv[g][r], -20.0f, 20.0f);   // :229
+                    for (int r = 0; r < 4; ++r) c.dv[g][r] = tclamp(c.dv[g][r], -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);   // :229
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
@@ -571,9 +535,9 @@ __global__ __launch_bounds__(THREADS) void colupdate_kernel(TiledArgs a, int k, 
         return *(const f32x4*)(ys + 4 * ((size_t)sl * RC + ((p * CQ + g) ^ (sl & 15))));
     };
     float vclip_prev = 0.0f, gtmp;
-    if (k > 0) clips(a.variant, k - 1, gtmp, vclip_prev);
+    if (k > 0) iter_clips(a.variant, k - 1, gtmp, vclip_prev);
     float gclip = 0.0f, vclip = 0.0f;
-    if (!final_only) clips(a.variant, k, gclip, vclip);
+    if (!final_only) iter_clips(a.variant, k, gclip, vclip);
     const float* usrc = k == 0 ? a.U0 : a.Ubuf[0];
     float* Ucur = final_only ? a.U_out : a.Ubuf[0];       // in place: U_{k-1} -> U_k
     float* Yk = a.Y + (size_t)k * S;
@@ -663,7 +627,7 @@ __global__ __launch_bounds__(THREADS) void colupdate_kernel(TiledArgs a, int k, 
                     for (int hh = 0; hh < HALVES; ++hh)
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
-                            dv[nt][hh][r] = tclamp(dv[nt][hh][r], -20.0f, 20.0f);   // :229
+                            dv[nt][hh][r] = tclamp(dv[nt][hh][r], -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);   // :229
             }
         }
 #pragma unroll

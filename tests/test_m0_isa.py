@@ -18,6 +18,7 @@ import pytest
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                     "hyperparameter-gnn_unfolded-d-admm-main_amd", "csrc")
+HDRS = ("dadmm_internal.h", "dadmm_consensus.h", "dadmm_device.h")
 HIPCC = "/opt/rocm/bin/hipcc"
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fno-slp-vectorize", "-mllvm", "-pragma-unroll-threshold=1000000"]
@@ -29,7 +30,9 @@ def _asm(src, tmp_path, defs=()):
     # the build's own assembly (csrc/Makefile ASMCHK) when it is up to date, else compile it here
     name = "dadmm_fused_rec.s" if defs else src.replace(".hip", ".s")
     built = os.path.join(CSRC, "build", name)
-    if os.path.exists(built) and os.path.getmtime(built) >= os.path.getmtime(os.path.join(CSRC, src)):
+    # (up to date: no older than the source or any header the kernels take their primitives from)
+    deps = [os.path.join(CSRC, f) for f in (src, *HDRS)]
+    if os.path.exists(built) and os.path.getmtime(built) >= max(os.path.getmtime(f) for f in deps):
         with open(built) as f:
             return f.read().splitlines()
     out = tmp_path / (os.path.basename(src) + ".s")
