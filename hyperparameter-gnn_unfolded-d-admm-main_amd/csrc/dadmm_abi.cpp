@@ -265,6 +265,40 @@ SplitPlan split_plan(const dadmm_dims* d) {
     sp.bytes = (size_t)groups * 2 * d->P * 4 * S * 1024;
     return sp;
 }
+
+int split_impl(const dadmm_dims* d, const void* op, const float* b, const uint64_t* nbr,
+               const uint32_t* nbr_order, const float* deg, const float* hyp, const float* y0,
+               const float* U0, const float* d0, float* Y, float* Grec, float* Urec, float* U_out,
+               int32_t* status, void* flags, void* scratch, void* stream, bool rec) {
+    int rc = check_dims(d);
+    if (rc) return rc;
+    if (d->B == 0 || d->K == 0) return ok();
+    if (rec && (any_null(Grec, Urec) || !all_aligned16(Grec, Urec)))
+        return fail(DADMM_EINVAL, "Grec and Urec must be non-NULL and 16-byte aligned");
+    if (any_null(op, b, nbr, deg, hyp, y0, U0, d0, Y, flags, scratch))
+        return fail(DADMM_EINVAL, "a required pointer is NULL");
+    if (!all_aligned16(op, Y, y0, U0, d0, flags, scratch, U_out))
+        return fail(DADMM_EINVAL, "op, Y, y0, U0, d0, U_out, flags and scratch must be 16-byte aligned");
+    int graph = 0, nt = 0;
+    if ((rc = check_fused_shape(d, nbr_order, &graph, &nt)) != DADMM_OK) return rc;
+    const SplitPlan sp = split_plan(d);
+    if (sp.groups == 0)
+        return fail(DADMM_EUNSUPPORTED, "the column-split forward does not serve B=%d P=%d n=%d "
+                    "(n_pad 128 or 256, P <= 6, ceil(B/16) <= CUs/2)", d->B, d->P, d->n);
+    dadmm::split_fn_ptr fn = rec ? dadmm::find_split_rec(d->P, nt, graph) : dadmm::find_split(d->P, nt, graph);
+    if (fn == nullptr)
+        return fail(DADMM_EUNSUPPORTED, "no split kernel for P=%d n_pad=%d", d->P, 64 * nt);
+    dadmm::SplitArgs sa;
+    fill_fused(sa.f, d, op, b, nbr, nbr_order, deg, hyp, y0, U0, d0, Y, U_out, status);
+    sa.f.Grec = Grec;
+    sa.f.Urec = Urec;
+    sa.xflag = (uint32_t*)flags;
+    sa.xbuf = (float*)scratch;
+    sa.groups = sp.groups;
+    sa.tiles = sp.tiles;
+    sa.spin_ticks = 20000000ull;   // 0.2 s at the 100 MHz s_memrealtime clock
+    return hip_rc(fn(sa, (hipStream_t)stream), "split launch");
+}
 }  // namespace
 
 size_t dadmm_split_scratch_bytes(const dadmm_dims* d) {
@@ -281,30 +315,17 @@ int dadmm_forward_split(const dadmm_dims* d, const void* op, const float* b, con
                         const uint32_t* nbr_order, const float* deg, const float* hyp,
                         const float* y0, const float* U0, const float* d0, float* Y, float* U_out,
                         int32_t* status, void* flags, void* scratch, void* stream) {
-    int rc = check_dims(d);
-    if (rc) return rc;
-    if (d->B == 0 || d->K == 0) return ok();
-    if (any_null(op, b, nbr, deg, hyp, y0, U0, d0, Y, flags, scratch))
-        return fail(DADMM_EINVAL, "a required pointer is NULL");
-    if (!all_aligned16(op, Y, y0, U0, d0, flags, scratch, U_out))
-        return fail(DADMM_EINVAL, "op, Y, y0, U0, d0, U_out, flags and scratch must be 16-byte aligned");
-    int graph = 0, nt = 0;
-    if ((rc = check_fused_shape(d, nbr_order, &graph, &nt)) != DADMM_OK) return rc;
-    const SplitPlan sp = split_plan(d);
-    if (sp.groups == 0)
-        return fail(DADMM_EUNSUPPORTED, "the column-split forward does not serve B=%d P=%d n=%d "
-                    "(n_pad 128 or 256, P <= 6, ceil(B/16) <= CUs/2)", d->B, d->P, d->n);
-    dadmm::split_fn_ptr fn = dadmm::find_split(d->P, nt, graph);
-    if (fn == nullptr)
-        return fail(DADMM_EUNSUPPORTED, "no split kernel for P=%d n_pad=%d", d->P, 64 * nt);
-    dadmm::SplitArgs sa;
-    fill_fused(sa.f, d, op, b, nbr, nbr_order, deg, hyp, y0, U0, d0, Y, U_out, status);
-    sa.xflag = (uint32_t*)flags;
-    sa.xbuf = (float*)scratch;
-    sa.groups = sp.groups;
-    sa.tiles = sp.tiles;
-    sa.spin_ticks = 20000000ull;   // 0.2 s at the 100 MHz s_memrealtime clock
-    return hip_rc(fn(sa, (hipStream_t)stream), "split launch");
+    return split_impl(d, op, b, nbr, nbr_order, deg, hyp, y0, U0, d0, Y, nullptr, nullptr, U_out, status,
+                      flags, scratch, stream, false);
+}
+
+int dadmm_forward_split_record(const dadmm_dims* d, const void* op, const float* b, const uint64_t* nbr,
+                               const uint32_t* nbr_order, const float* deg, const float* hyp,
+                               const float* y0, const float* U0, const float* d0, float* Y, float* Grec,
+                               float* Urec, float* U_out, int32_t* status, void* flags, void* scratch,
+                               void* stream) {
+    return split_impl(d, op, b, nbr, nbr_order, deg, hyp, y0, U0, d0, Y, Grec, Urec, U_out, status,
+                      flags, scratch, stream, true);
 }
 
 size_t dadmm_backward_scratch_bytes(const dadmm_dims* d) {

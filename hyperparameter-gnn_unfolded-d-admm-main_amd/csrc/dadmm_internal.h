@@ -45,7 +45,7 @@ fused_fn_ptr find_fused_rec(int P, int nt, int graph);
 // ---- the column-split forward for small batches (dadmm_split.hip) ------------------------------
 constexpr int SPLIT_COLS = 64;   // columns of n_pad per slice (one workgroup each)
 struct SplitArgs {
-    FusedArgs f;         // as the fused kernel (U_out / status optional; no recording)
+    FusedArgs f;         // as the fused kernel (U_out / status optional; Grec / Urec: find_split_rec only)
     float* xbuf;         // [groups][2][P][4][S][256] GEMM1 partial tiles (no initialisation)
     uint32_t* xflag;     // [groups][P][4][S] epoch words + 1 abort word: ZEROED before every launch
     int groups;          // workgroup groups (S blocks each); grid = groups * S <= CUs
@@ -55,6 +55,8 @@ struct SplitArgs {
 typedef hipError_t (*split_fn_ptr)(const SplitArgs&, hipStream_t);
 // P = 1..6, n_pad = 64 * nt with nt in {2, 4}; nullptr otherwise
 split_fn_ptr find_split(int P, int nt, int graph);
+// Same shapes, recording the adjoint's trajectory (sa.f.Grec / sa.f.Urec must be set).
+split_fn_ptr find_split_rec(int P, int nt, int graph);
 
 // ---- adjoint (dadmm_backward.hip) ---------------------------------------------------------------
 struct BackwardArgs {

@@ -32,6 +32,10 @@
 // launch-wide abort word and status bit 16, every wave then skips its remaining waits and runs to
 // the end, and the caller's gated stepwise launch recomputes the batch exactly.
 //
+// Training (DADMM_SPLIT_REC, below): the recording form also stores the adjoint's trajectory, Grec[k]
+// (the gradient before its clamp) and Urec[k] (U_k entering iteration k), [K][B][P][n] like Y, from
+// the lane that stores those rows of Y[k]. Nothing else differs: same exchange, same Y / U_out bits.
+//
 // Reduction order: every chain as dadmm_fused.hip (0,4,8,12, 1,5,... inside each 16-block, blocks
 // ascending; -ffp-contract=off elsewhere), GEMM1 cut at slice boundaries as above.
 
@@ -41,6 +45,14 @@
 #include "dadmm_internal.h"
 #include "dadmm_consensus.h"
 #include "dadmm_device.h"
+
+// This file is compiled twice (csrc/Makefile), like dadmm_fused.hip: DADMM_SPLIT_REC = 0 defines
+// find_split (inference), DADMM_SPLIT_REC = 1 defines find_split_rec (training: the kernel also
+// stores the adjoint's trajectory Grec / Urec). The recording is a compile-time variant (REC) with
+// a kernel of its own, so the inference kernels are the same code with or without it.
+#ifndef DADMM_SPLIT_REC
+#define DADMM_SPLIT_REC 0
+#endif
 
 namespace dadmm {
 namespace split {
@@ -87,7 +99,9 @@ __device__ __forceinline__ bool wait_tiles(const uint32_t* const (&words)[TH > 0
 
 // One wave's share of the split forward. HALF = w / 4: agents HALF, HALF + 2, ... (TH of them);
 // GEMM1 m-block mb = w % 4 of those agents, GEMM2 / state n-tile nt = w % 4 of the slice.
-template <int P, int NT, int GRAPH, int HALF>
+// REC (training): also stores Grec[k] (the gradient before its clamp) and Urec[k] (U_k entering
+// iteration k) beside Y[k], as dadmm_fused.hip's recording form does.
+template <int P, int NT, int GRAPH, int HALF, bool REC>
 __device__ __forceinline__ void split_body(const SplitArgs& sa, float* __restrict__ lds, const int w) {
     constexpr int S = NT;                            // slices of n_pad = 64 NT
     constexpr int NP = NT * 64;
@@ -309,6 +323,11 @@ __device__ __forceinline__ void split_body(const SplitArgs& sa, float* __restric
             // ---- GEMM2 G_p[n-tile nt] = A_p[:, slice]^T R_p, gradient assembly, clamps, primal
             //      update (:69-93) -> Ylds and Y[k] ---------------------------------------------
             const rsrc_t rY = make_rsrc(a.Y + (size_t)k * B * P * n, state_bytes);
+            [[maybe_unused]] rsrc_t rG, rUr;
+            if constexpr (REC) {
+                rG = make_rsrc(a.Grec + (size_t)k * B * P * n, state_bytes);
+                rUr = make_rsrc(a.Urec + (size_t)k * B * P * n, state_bytes);
+            }
             bool bad_g = false;
             __builtin_amdgcn_s_setprio(2);
 #pragma unroll
@@ -325,6 +344,7 @@ __device__ __forceinline__ void split_body(const SplitArgs& sa, float* __restric
                 float* yrow = Ylds + (p * BT + j) * YS + 16 * nt + 4 * h;
                 const f32x4 yk = *(const f32x4*)yrow;
                 f32x4 yn;
+                [[maybe_unused]] f32x4 grv, urv;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float yv = yk[r];
@@ -333,13 +353,23 @@ __device__ __forceinline__ void split_body(const SplitArgs& sa, float* __restric
                     gr = gr + sign_times(yv, ta[i]);
                     gr = gr + U[i][r] * dg[p];
                     gr = gr + D[i][r] * rh[i];
+                    if constexpr (REC) {
+                        grv[r] = gr;
+                        urv[r] = U[i][r];
+                    }
                     bad_g |= (gr != gr);                            // :84 guard (flag only)
                     gr = mclamp(gr, -gclip, gclip);                 // :80-81
                     float v = yv - al[i] * gr;                      // :89
                     yn[r] = mclamp(v, -vclip, vclip);               // :92-93
                 }
                 *(f32x4*)yrow = yn;
-                bstore4<16>(yn, rY, rows_ok ? voffY + (uint32_t)(p * n * 4) : 0x80000000u);
+                // Y[k][s][p][n0..n0+3]; rows past n go to an offset the range check drops
+                const uint32_t o = rows_ok ? voffY + (uint32_t)(p * n * 4) : 0x80000000u;
+                bstore4<16>(yn, rY, o);
+                if constexpr (REC) {   // written once, never re-read here: sc1 like Y[k]
+                    bstore4<16>(grv, rG, o);
+                    bstore4<16>(urv, rUr, o);
+                }
             }
             __builtin_amdgcn_s_setprio(0);
             status |= bad_g ? 4u : 0u;
@@ -388,46 +418,67 @@ __global__ __launch_bounds__(WV * 64) void split_forward_kernel(SplitArgs sa) {
     __shared__ __attribute__((aligned(16))) float lds[P * M_PAD * AST + P * BT * (YS + RS)];
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (w < 4)
-        split_body<P, NT, GRAPH, 0>(sa, lds, w);
+        split_body<P, NT, GRAPH, 0, false>(sa, lds, w);
     else
-        split_body<P, NT, GRAPH, 1>(sa, lds, w);
+        split_body<P, NT, GRAPH, 1, false>(sa, lds, w);
 }
 
+// The recording form (sa.f.Grec / sa.f.Urec set): same exchange, same Y / U_out.
 template <int P, int NT, int GRAPH>
+__global__ __launch_bounds__(WV * 64) void split_forward_rec_kernel(SplitArgs sa) {
+    __shared__ __attribute__((aligned(16))) float lds[P * M_PAD * AST + P * BT * (YS + RS)];
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (w < 4)
+        split_body<P, NT, GRAPH, 0, true>(sa, lds, w);
+    else
+        split_body<P, NT, GRAPH, 1, true>(sa, lds, w);
+}
+
+// (the host-side templates carry REC so that the two objects' instantiations are distinct symbols)
+template <int P, int NT, int GRAPH, bool REC>
 hipError_t launch_split(const SplitArgs& sa, hipStream_t stream) {
-    hipLaunchKernelGGL((split_forward_kernel<P, NT, GRAPH>), dim3(sa.groups * NT), dim3(WV * 64), 0,
-                       stream, sa);
+    if constexpr (REC)
+        hipLaunchKernelGGL((split_forward_rec_kernel<P, NT, GRAPH>), dim3(sa.groups * NT), dim3(WV * 64),
+                           0, stream, sa);
+    else
+        hipLaunchKernelGGL((split_forward_kernel<P, NT, GRAPH>), dim3(sa.groups * NT), dim3(WV * 64), 0,
+                           stream, sa);
     return hipGetLastError();
 }
 
-template <int P, int NT>
+template <int P, int NT, bool REC>
 split_fn_ptr pick_graph(int graph) {
     switch (graph) {
-        case GRAPH_SHARED: return &launch_split<P, NT, GRAPH_SHARED>;
-        case GRAPH_LANE: return &launch_split<P, NT, GRAPH_LANE>;
-        case GRAPH_ORDERED: return &launch_split<P, NT, GRAPH_ORDERED>;
+        case GRAPH_SHARED: return &launch_split<P, NT, GRAPH_SHARED, REC>;
+        case GRAPH_LANE: return &launch_split<P, NT, GRAPH_LANE, REC>;
+        case GRAPH_ORDERED: return &launch_split<P, NT, GRAPH_ORDERED, REC>;
         default: return nullptr;
     }
 }
 
-template <int P>
+template <int P, bool REC>
 split_fn_ptr pick_nt(int nt, int graph) {
-    if (nt == 2) return pick_graph<P, 2>(graph);
-    if (nt == 4) return pick_graph<P, 4>(graph);
+    if (nt == 2) return pick_graph<P, 2, REC>(graph);
+    if (nt == 4) return pick_graph<P, 4, REC>(graph);
     return nullptr;
 }
 
 }  // namespace split
 
 // Instantiated shapes: P = 1..6, n_pad = 128 or 256 (S = 2 or 4 slices of 64 columns), m_pad = 64.
+#if DADMM_SPLIT_REC
+split_fn_ptr find_split_rec(int P, int nt, int graph) {
+#else
 split_fn_ptr find_split(int P, int nt, int graph) {
+#endif
+    constexpr bool REC = DADMM_SPLIT_REC != 0;
     switch (P) {
-        case 1: return split::pick_nt<1>(nt, graph);
-        case 2: return split::pick_nt<2>(nt, graph);
-        case 3: return split::pick_nt<3>(nt, graph);
-        case 4: return split::pick_nt<4>(nt, graph);
-        case 5: return split::pick_nt<5>(nt, graph);
-        case 6: return split::pick_nt<6>(nt, graph);
+        case 1: return split::pick_nt<1, REC>(nt, graph);
+        case 2: return split::pick_nt<2, REC>(nt, graph);
+        case 3: return split::pick_nt<3, REC>(nt, graph);
+        case 4: return split::pick_nt<4, REC>(nt, graph);
+        case 5: return split::pick_nt<5, REC>(nt, graph);
+        case 6: return split::pick_nt<6, REC>(nt, graph);
         default: return nullptr;
     }
 }

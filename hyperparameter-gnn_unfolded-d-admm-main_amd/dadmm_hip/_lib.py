@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # scripts/time_variants.sh); it is still the HIP library, there is no other path
 LIB_PATH = os.environ.get("DADMM_LIB_VARIANT") or os.path.join(_HERE, "libdadmm.so")
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 DADMM_OK, DADMM_EINVAL, DADMM_EUNSUPPORTED, DADMM_EHIP = 0, -1, -2, -3
 VARIANT_UNFOLDED, VARIANT_GNN = 0, 1
 STATUS_Y_NONFINITE, STATUS_U_NONFINITE, STATUS_GRAD_NAN, STATUS_YNEXT_NAN = 1, 2, 4, 8
@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = (
     "dadmm_split_scratch_bytes",
     "dadmm_split_flag_bytes",
     "dadmm_forward_split",
+    "dadmm_forward_split_record",
     "dadmm_stepwise_scratch_bytes",
     "dadmm_forward_stepwise",
     "dadmm_backward_scratch_bytes",
@@ -179,6 +180,8 @@ def load() -> ctypes.CDLL:
     L.dadmm_split_flag_bytes.argtypes = [ctypes.POINTER(Dims)]
     L.dadmm_forward_split.restype = ctypes.c_int
     L.dadmm_forward_split.argtypes = [ctypes.POINTER(Dims)] + [vp] * 15
+    L.dadmm_forward_split_record.restype = ctypes.c_int
+    L.dadmm_forward_split_record.argtypes = [ctypes.POINTER(Dims)] + [vp] * 17
     L.dadmm_stepwise_scratch_bytes.restype = ctypes.c_size_t
     L.dadmm_stepwise_scratch_bytes.argtypes = [ctypes.POINTER(Dims)]
     L.dadmm_forward_stepwise.restype = ctypes.c_int

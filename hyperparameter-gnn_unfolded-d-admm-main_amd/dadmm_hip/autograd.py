@@ -1,7 +1,8 @@
 """autograd plumbing for the HIP forward (the drivers call ``loss.backward()`` through it).
 
 Training-mode forwards (the hyper-parameter table requires grad) run the recording forward
-(``dadmm_forward_record``) and keep the trajectory; ``backward`` runs the adjoint kernel
+(``dadmm_forward_record``; with ``train_split`` and a small batch its column-split form,
+``dadmm_forward_split_record``) and keep the trajectory; ``backward`` runs the adjoint kernel
 (``dadmm_backward``) and returns d loss / d table, from which torch autograd continues into
 ``seq_hyp.param`` (cumsum / sigmoid / penalty / clamp of ``seq_hyperparam.table``).
 """
@@ -38,10 +39,10 @@ def check_status(status: torch.Tensor) -> int:
 
 class _UnfoldedFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, table, op, b, graphs, y0, U0, d0, variant):
+    def forward(ctx, table, op, b, graphs, y0, U0, d0, variant, train_split=False):
         record = ctx.needs_input_grad[0]
         out = forward_raw(op, b, graphs, table.detach(), y0, U0, d0, variant=variant,
-                          record=record)
+                          record=record, train_split=bool(train_split) and record)
         Y, _, status = out[:3]
         if _WARN:   # the reference's warnings (bit 16 is internal: the exact recomputation ran)
             for msg in describe_status(check_status(status) & ~_lib.STATUS_RECOMPUTE):
@@ -63,7 +64,7 @@ class _UnfoldedFn(torch.autograd.Function):
                 + "; ".join(describe_status(st)) + ") is not supported by the adjoint kernel")
         dtable = backward_raw(ctx.op, ctx.graphs, ctx.traj, gY)
         ctx.traj = None
-        return dtable, None, None, None, None, None, None, None
+        return dtable, None, None, None, None, None, None, None, None
 
 
 def tag_status(Y: torch.Tensor, status: torch.Tensor) -> torch.Tensor:
@@ -95,7 +96,9 @@ def raise_if_timed_out(Y: torch.Tensor) -> None:
         check_status(status)
 
 
-def dadmm_unfolded_apply(op, b, graphs, table, y0, U0, d0, variant=_lib.VARIANT_UNFOLDED):
+def dadmm_unfolded_apply(op, b, graphs, table, y0, U0, d0, variant=_lib.VARIANT_UNFOLDED,
+                         train_split=False):
     """(Y [K,B,P,n], status [1] int32 device tensor) = the K-step recurrence with the reference's
-    guards; Y is differentiable w.r.t. ``table`` (adjoint kernel)."""
-    return _UnfoldedFn.apply(table, op, b, graphs, y0, U0, d0, variant)
+    guards; Y is differentiable w.r.t. ``table`` (adjoint kernel). ``train_split``: a recording
+    forward of a small batch takes the column-split kernel (forward_raw's ``train_split``)."""
+    return _UnfoldedFn.apply(table, op, b, graphs, y0, U0, d0, variant, train_split)

@@ -106,7 +106,7 @@ def draw_inits(shape, device, n_store=None, zero=None, nzero=0):
 def forward_raw(op: PreparedOperator, b: torch.Tensor, graphs: GraphBatch, hyp: torch.Tensor,
                 y0: torch.Tensor = None, U0: torch.Tensor = None, d0: torch.Tensor = None, *,
                 variant: int = _lib.VARIANT_UNFOLDED, want_U: bool = False, path: str = "auto",
-                record: bool = False):
+                record: bool = False, train_split: bool = False):
     """The K-step forward with the reference's NaN/Inf guards, enqueued on the current stream
     (no host synchronisation). Shapes: b [B,P,m], hyp [K,H,4], y0/U0/d0 [B,P,n].
 
@@ -118,6 +118,11 @@ def forward_raw(op: PreparedOperator, b: torch.Tensor, graphs: GraphBatch, hyp: 
     alone do NOT apply the guards: their status only flags them).
 
     record: also store the trajectory the adjoint consumes (training; dadmm_forward_record).
+    By default a recording forward keeps the fused order at every batch size. train_split (with
+    path "auto") or path "split" opts into the recording column-split forward
+    (dadmm_forward_split_record) for the batches the inference path splits: the iterates AND the
+    trajectory then follow the split GEMM1 order (``split_cols``), which differs from the fused
+    order in fp32 rounding; the adjoints consume either trajectory.
 
     y0 = U0 = d0 = None: the reference's random inits are drawn by the prologue launch
     (draw_inits; bit-identical to torch.randn * 1e-2 from the device's default generator).
@@ -151,13 +156,18 @@ def forward_raw(op: PreparedOperator, b: torch.Tensor, graphs: GraphBatch, hyp: 
         raise ValueError("the fused kernel follows non-ascending adjacency orders only for "
                          "P <= 8; use path='auto' or 'stepwise'")
     # small batches (the fused tiles would fill at most half the CUs): the column-split forward
-    split_b = 0
+    split_b = flag_b = 0
     if path in ("auto", "split") and not record and graphs.fused_ok:
         split_b = L.dadmm_split_scratch_bytes(ctypes.byref(d))
+        flag_b = L.dadmm_split_flag_bytes(ctypes.byref(d)) if split_b else 0
+    elif record and graphs.fused_ok and (path == "split" or (path == "auto" and train_split)):
+        # training opt-in: the sizes depend on b.device's CU count
+        with torch.cuda.device(b.device):
+            split_b = L.dadmm_split_scratch_bytes(ctypes.byref(d))
+            flag_b = L.dadmm_split_flag_bytes(ctypes.byref(d)) if split_b else 0
     if path == "split" and split_b == 0:
         raise ValueError(f"the column-split forward does not serve B={B} P={P} n={ns} "
                          "(n_pad 128 or 256, P <= 6, m <= 64, ceil(B/16) <= CUs/2)")
-    flag_b = L.dadmm_split_flag_bytes(ctypes.byref(d)) if split_b else 0
     # one device allocation: [status word | 252 B pad | split epoch words | stepwise scratch
     # (guard flags first)]; the prologue zeroes the status word, the epoch words and the guard
     # flags in the same launch as the draws
@@ -179,10 +189,17 @@ def forward_raw(op: PreparedOperator, b: torch.Tensor, graphs: GraphBatch, hyp: 
         fused = path in ("auto", "fused", "split") and graphs.fused_ok
         if split_b:
             xbuf = torch.empty(split_b, dtype=torch.uint8, device=b.device)
-            _lib.check("dadmm_forward_split", L.dadmm_forward_split(
-                ctypes.byref(d), _ptr(op.workspace), _ptr(b), _ptr(graphs.nbr), _ptr(graphs.order),
-                _ptr(graphs.deg), _ptr(hyp), _ptr(y0), _ptr(U0), _ptr(d0), _ptr(Y), _ptr(U),
-                _ptr(status), _ptr(sflags), _ptr(xbuf), stream))
+            if record:
+                _lib.check("dadmm_forward_split_record", L.dadmm_forward_split_record(
+                    ctypes.byref(d), _ptr(op.workspace), _ptr(b), _ptr(graphs.nbr),
+                    _ptr(graphs.order), _ptr(graphs.deg), _ptr(hyp), _ptr(y0), _ptr(U0), _ptr(d0),
+                    _ptr(Y), _ptr(Grec), _ptr(Urec), _ptr(U), _ptr(status), _ptr(sflags),
+                    _ptr(xbuf), stream))
+            else:
+                _lib.check("dadmm_forward_split", L.dadmm_forward_split(
+                    ctypes.byref(d), _ptr(op.workspace), _ptr(b), _ptr(graphs.nbr),
+                    _ptr(graphs.order), _ptr(graphs.deg), _ptr(hyp), _ptr(y0), _ptr(U0), _ptr(d0),
+                    _ptr(Y), _ptr(U), _ptr(status), _ptr(sflags), _ptr(xbuf), stream))
         elif fused:
             if record:
                 rc = L.dadmm_forward_record(
@@ -240,13 +257,17 @@ def forward_raw(op: PreparedOperator, b: torch.Tensor, graphs: GraphBatch, hyp: 
 
 
 def split_cols(op: PreparedOperator, B: int, K: int, graphs: GraphBatch = None, hyp_rows: int = 1,
-               record: bool = False) -> int:
+               record: bool = False, train_split: bool = False) -> int:
     """The GEMM1 slice width forward_raw's "auto" path uses for this batch: 64 when it runs the
-    column-split forward (dadmm_forward_split), else 0 (the oracle's ``split_cols`` argument)."""
-    if record or (graphs is not None and not graphs.fused_ok):
+    column-split forward (dadmm_forward_split; with ``record``, dadmm_forward_split_record, which
+    needs ``train_split``), else 0 (the oracle's ``split_cols`` argument)."""
+    if (record and not train_split) or (graphs is not None and not graphs.fused_ok):
         return 0
     shared = graphs.shared if graphs is not None else 1
     d = op.dims(B=B, K=K, hyp_rows=hyp_rows, graph_shared=shared)
+    if record:
+        with torch.cuda.device(op.device):
+            return 64 if _lib.load().dadmm_split_scratch_bytes(ctypes.byref(d)) else 0
     return 64 if _lib.load().dadmm_split_scratch_bytes(ctypes.byref(d)) else 0
 
 

@@ -86,7 +86,8 @@ def validate(model, b_va, x_va, graph, args, bs, gen, rank, world, device):
     return tot / max(nb, 1), hyp
 
 
-def main(argv=None):
+def build_parser():
+    """configurations.build_parser() plus this driver's own options."""
     ap = configurations.build_parser()
     ap.add_argument("--out", default=None, help="output directory (default: save_dir/<time>)")
     ap.add_argument("--patience", type=int, default=70)
@@ -95,7 +96,16 @@ def main(argv=None):
                          "rank draws its shard's (independent streams per rank); 'global' = every "
                          "rank draws the whole batch's and keeps its slice (bit-identical "
                          "per-sample forwards for any world size; costs B/shard x the draws)")
-    args = ap.parse_args(argv)
+    ap.add_argument("--train-split", action="store_true",
+                    help="training forwards of small batches (ceil(B/16) <= CUs/2, n_pad 128 or "
+                         "256) run the recording column-split kernel "
+                         "(DLASSO_unfolded.train_split): the iterates then follow the split GEMM1 "
+                         "order, which differs from the fused order in fp32 rounding")
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     rank, world, local = D.init_from_env()
     if torch.cuda.is_available() and args.device.startswith("cuda"):
         # one process per GPU; ranks beyond the visible devices share them (gloo rehearsals)
@@ -121,6 +131,7 @@ def main(argv=None):
     graph = nx.erdos_renyi_graph(args.P, args.graph_prob, seed=seed)
 
     model = unfolded_DLASSO.DLASSO_unfolded(A=A, args=args).to(device)
+    model.train_split = bool(args.train_split)
     optimizer = torch.optim.Adam(model.parameters(), lr=args.lr, amsgrad=False)
     scheduler = ReduceLROnPlateau(optimizer, mode="min", factor=0.8, patience=3, min_lr=1e-6)
 

@@ -45,6 +45,11 @@ class DLASSO_unfolded(nn.Module):
         self.last_status = None
         self._table = None
         self._table_key = None
+        # opt-in (train_unfolded.py --train-split): a training forward (the table requires grad)
+        # of a small batch runs the recording column-split kernel (dadmm_forward_split_record).
+        # Its iterates follow the split GEMM1 order, which differs from the fused order in fp32
+        # rounding. A plain attribute: no buffer, no parameter; CPU tensors ignore it.
+        self.train_split = False
 
     # The reference precomputes AtA eagerly (:16). The HIP path never forms it; it is kept as a
     # lazily computed attribute for callers that read it.
@@ -125,7 +130,8 @@ class DLASSO_unfolded(nn.Module):
 
         table = self.hyp_table(K)                       # [K, H, 4]
         Y, self.last_status = dadmm_unfolded_apply(self.operator(), bb, graphs, table, y0, U0,
-                                                   d0, _lib.VARIANT_UNFOLDED)
+                                                   d0, _lib.VARIANT_UNFOLDED,
+                                                   train_split=bool(self.train_split))
         hyp = table[K - 1].unsqueeze(-1)                # seq_hyp(K-1): [H, 4, 1]
         return tag_status(Y.unsqueeze(-1), self.last_status), hyp
 

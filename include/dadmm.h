@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define DADMM_ABI_VERSION 18
+#define DADMM_ABI_VERSION 19
 
 enum {
     DADMM_OK = 0,
@@ -86,7 +86,7 @@ enum {
     DADMM_STATUS_YNEXT_NAN = 8,      /* y_next had NaN/Inf                           (:102)  */
     DADMM_STATUS_RECOMPUTE = 16,     /* dadmm_forward only: the shared adjacency is not
                                       * symmetric, so the fused consensus cannot follow it;
-                                      * dadmm_forward_split: a wait between slices timed out;
+                                      * dadmm_forward_split(_record): a wait between slices timed out;
                                       * the gated stepwise run recomputes the batch (never set
                                       * after a gated run)                                    */
     DADMM_STATUS_BARRIER_TIMEOUT = 0x100 /* gated stepwise run could not synchronise its grid
@@ -164,6 +164,27 @@ int dadmm_forward_record(const dadmm_dims* d, const void* op, const float* b, co
                          const uint32_t* nbr_order, const float* deg, const float* hyp,
                          const float* y0, const float* U0, const float* d0, float* Y, float* Grec,
                          float* Urec, float* U_out, int32_t* status, void* stream);
+
+/* dadmm_forward_split that also records the adjoint's trajectory (ABI 19): the training-mode
+ * forward for SMALL batches, which the reference's drivers train on (B = 16-64).
+ * Replaces: DLASSO_unfolded.forward's loop body (unfolded_DLASSO.py:45, 53-109) under the drivers'
+ *           loss.backward() (unfolded_train_new.py:74-80), as dadmm_forward_record does.
+ *   Grec [K][B][P][n]: the gradient of iteration k BEFORE its clamp (unfolded_DLASSO.py:73-77)
+ *   Urec [K][B][P][n]: U_k entering iteration k (Urec[0] = U0)
+ * both non-NULL and 16-byte aligned (else DADMM_EINVAL), same layout as dadmm_forward_record's.
+ * Y and U_out are bit-identical to dadmm_forward_split's, i.e. the split GEMM1 order
+ * (oracle_forward_f32_split(split_cols = 64)), NOT dadmm_forward_record's: Grec / Urec are that
+ * order's own trajectory, and dadmm_backward / dadmm_adjoint consume it unchanged (they read only
+ * Y, Grec, Urec, y0, d0 and re-derive the clamp masks from those values).
+ * Shapes, `flags` / `scratch` (dadmm_split_flag_bytes / dadmm_split_scratch_bytes serve both
+ * entries), the bounded waits and the `status` contract: dadmm_forward_split's. After
+ * DADMM_STATUS_RECOMPUTE or a guard bit the gated dadmm_forward_stepwise, given the same Grec /
+ * Urec, re-records the batch exactly (in the unsplit order). */
+int dadmm_forward_split_record(const dadmm_dims* d, const void* op, const float* b, const uint64_t* nbr,
+                               const uint32_t* nbr_order, const float* deg, const float* hyp,
+                               const float* y0, const float* U0, const float* d0, float* Y,
+                               float* Grec, float* Urec, float* U_out, int32_t* status, void* flags,
+                               void* scratch, void* stream);
 
 /* Bits of the `gate` argument of dadmm_forward_stepwise. */
 enum {
