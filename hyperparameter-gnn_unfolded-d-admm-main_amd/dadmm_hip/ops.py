@@ -7,6 +7,8 @@ current HIP stream.
 from __future__ import annotations
 
 import ctypes
+import dataclasses
+import types
 
 import torch
 
@@ -16,9 +18,7 @@ from .graph import GraphBatch
 
 def _dev_check(*tensors):
     for t in tensors:
-        if t is None:
-            continue
-        if t.device.type != "cuda":
+        if t is not None and t.device.type != "cuda":
             raise RuntimeError(
                 "dadmm_hip runs on a ROCm GPU only (tensors must be on a cuda/hip device); "
                 f"got a tensor on {t.device}")
@@ -103,6 +103,71 @@ def draw_inits(shape, device, n_store=None, zero=None, nzero=0):
     return y0, U0, d0
 
 
+@dataclasses.dataclass(frozen=True)
+class ForwardPlan:
+    """What one forward launches (plan_forward): a decision over the Dims alone."""
+    candidates: tuple       # launcher names (_FORWARD_LAUNCHERS), tried in this order
+    gated: bool             # the stepwise launch follows
+    split_bytes: int        # the split launch's exchange buffer (0: "split" is no candidate)
+    split_flag_bytes: int   # its epoch words
+    stepwise_bytes: int     # the stepwise scratch, guard flags first (0 unless gated)
+    nzero: int              # int32 words the prologue zeroes: status + pad, epochs, guard flags
+
+
+def plan_forward(d: _lib.Dims, fused_ok: bool, *, path: str = "auto", record: bool = False,
+                 train_split: bool = False) -> ForwardPlan:
+    """The dispatch table of forward_raw's docstring as data. No tensors, no allocation, no
+    launch: only the library's size queries, which depend on the CURRENT device's CU count
+    (callers enter ``torch.cuda.device`` first). fused_ok: GraphBatch.fused_ok."""
+    if path not in ("auto", "fused", "split", "tiled", "stepwise"):
+        raise ValueError(f"unknown path {path!r}")
+    if path in ("fused", "split") and not fused_ok:
+        raise ValueError("the fused kernel follows non-ascending adjacency orders only for "
+                         "P <= 8; use path='auto' or 'stepwise'")
+    L, dp = _lib.load(), ctypes.byref(d)
+    # small batches split the columns; a recording forward only where train_split opts in
+    try_split = path == "split" or (path == "auto" and fused_ok and (not record or train_split))
+    split_b = L.dadmm_split_scratch_bytes(dp) if try_split else 0
+    if path == "split" and not split_b:
+        raise ValueError(f"the column-split forward does not serve B={d.B} P={d.P} n={d.n} "
+                         "(n_pad 128 or 256, P <= 6, m <= 64, ceil(B/16) <= CUs/2)")
+    tiled = "tiled_record" if record else "tiled"
+    table = {"auto": ("fused", tiled) if fused_ok else (tiled,), "fused": ("fused",),
+             "tiled": (tiled,), "stepwise": ()}
+    candidates = ("split",) if split_b else table[path]
+    gated = path in ("auto", "stepwise")
+    flag_b = L.dadmm_split_flag_bytes(dp) if split_b else 0
+    return ForwardPlan(candidates, gated, split_b, flag_b,
+                       L.dadmm_stepwise_scratch_bytes(dp) if gated else 0,
+                       (256 + flag_b + (_sw_flag_bytes(d.K) if gated else 0)) // 4)
+
+
+# The forward launchers. ``a`` (forward_raw) holds what they share: the two pointer prefixes
+# (d, op, b, <graph>, deg, hyp, y0, U0, d0, Y), each built once, and the pieces of their tails.
+# Each returns (entry point, return code); the record bit picks the *_record entry, looked up on
+# the library at every call (bench.py times the kernel by replacing L.dadmm_forward).
+def _launch_fused(a):
+    fn = "dadmm_forward_record" if a.rec else "dadmm_forward"
+    return fn, getattr(a.L, fn)(*a.ordered, *a.rec, a.U, a.status, a.stream)
+
+
+def _launch_split(a):
+    fn = "dadmm_forward_split_record" if a.rec else "dadmm_forward_split"
+    xbuf = torch.empty(a.plan.split_bytes, dtype=torch.uint8, device=a.device)
+    return fn, getattr(a.L, fn)(*a.ordered, *a.rec, a.U, a.status, a.sflags, _ptr(xbuf), a.stream)
+
+
+def _launch_tiled(a):
+    fn = "dadmm_forward_tiled_record" if a.rec else "dadmm_forward_tiled"
+    tscratch = torch.empty(max(a.L.dadmm_tiled_scratch_bytes(a.dp), 256), dtype=torch.uint8,
+                           device=a.device)
+    return fn, getattr(a.L, fn)(*a.visits, *a.rec, a.U, a.status, _ptr(tscratch), a.stream)
+
+
+_FORWARD_LAUNCHERS = {"fused": _launch_fused, "split": _launch_split, "tiled": _launch_tiled,
+                      "tiled_record": _launch_tiled}
+
+
 def forward_raw(op: PreparedOperator, b: torch.Tensor, graphs: GraphBatch, hyp: torch.Tensor,
                 y0: torch.Tensor = None, U0: torch.Tensor = None, d0: torch.Tensor = None, *,
                 variant: int = _lib.VARIANT_UNFOLDED, want_U: bool = False, path: str = "auto",
@@ -110,19 +175,28 @@ def forward_raw(op: PreparedOperator, b: torch.Tensor, graphs: GraphBatch, hyp: 
     """The K-step forward with the reference's NaN/Inf guards, enqueued on the current stream
     (no host synchronisation). Shapes: b [B,P,m], hyp [K,H,4], y0/U0/d0 [B,P,n].
 
-    path "auto": the fused kernel when the shape is compiled (its column-split form,
-    dadmm_forward_split, for batches that fill at most half the CUs: GEMM1 in the split order,
-    ``split_cols``), otherwise the tiled kernel (one launch per iteration); either is followed by
-    the device-gated stepwise recomputation (runs only if a guard event was flagged). Training (record) outside the fused shapes: the stepwise
-    kernels, or the streamed single launch where it applies (P <= 16, m <= 64). "fused" / "split" / "tiled" / "stepwise" force one path ("fused" / "split" / "tiled"
-    alone do NOT apply the guards: their status only flags them).
+    What runs is plan_forward's table. Candidates are tried in order: on "auto" one that returns
+    DADMM_EUNSUPPORTED is skipped, anything else raises. gated: the stepwise launch follows; it
+    recomputes the batch only if a guard event was flagged (all of it if no candidate ran).
+    Forced "fused" / "split" / "tiled" do NOT apply the guards: their status only flags them.
 
-    record: also store the trajectory the adjoint consumes (training; dadmm_forward_record).
-    By default a recording forward keeps the fused order at every batch size. train_split (with
-    path "auto") or path "split" opts into the recording column-split forward
-    (dadmm_forward_split_record) for the batches the inference path splits: the iterates AND the
-    trajectory then follow the split GEMM1 order (``split_cols``), which differs from the fused
-    order in fp32 rounding; the adjoints consume either trajectory.
+      path      when                                              candidates             gated
+      auto      fused_ok, split serves, not record or train_split split                  yes
+      auto      fused_ok, otherwise                               fused, tiled[_record]  yes
+      auto      not fused_ok                                      tiled[_record]         yes
+      fused     fused_ok, else ValueError                         fused                  no
+      split     fused_ok and split serves, else ValueError        split                  no
+      tiled                                                       tiled[_record]         no
+      stepwise                                                    none                   yes
+
+    fused_ok: graphs.fused_ok. split serves: dadmm_split_scratch_bytes != 0 (n_pad 128 / 256,
+    P <= 6, m <= 64, the fused tiles fill at most half the CUs); GEMM1 then runs in the split
+    order (``split_cols``), which differs from the fused order in fp32 rounding.
+
+    record: also store the trajectory the adjoint consumes (the *_record entry of each launcher;
+    tiled_record is the streamed single launch, P <= 16, m <= 64; the stepwise kernels record
+    when they run). It keeps the fused order at every batch size unless train_split (ignored
+    without record) or path "split" opts into the split order; the adjoints consume either.
 
     y0 = U0 = d0 = None: the reference's random inits are drawn by the prologue launch
     (draw_inits; bit-identical to torch.randn * 1e-2 from the device's default generator).
@@ -133,142 +207,72 @@ def forward_raw(op: PreparedOperator, b: torch.Tensor, graphs: GraphBatch, hyp: 
     draw = y0 is None
     if draw != (U0 is None) or draw != (d0 is None):
         raise ValueError("pass all of y0, U0, d0 or none of them")
-    if path not in ("auto", "fused", "split", "tiled", "stepwise"):
-        raise ValueError(f"unknown path {path!r}")
     B, P, m = b.shape
     if P != op.P or m != op.m:
         raise ValueError(f"b is [B,{P},{m}], operator is P={op.P}, m={op.m}")
     K, H = int(hyp.shape[0]), int(hyp.shape[1])
-    ns = op.n_store
-    b = b.contiguous().float()
-    hyp = hyp.contiguous().float()
-    if not draw:
-        y0, U0, d0 = (_pad_n(x, ns).contiguous().float() for x in (y0, U0, d0))
-    Y = torch.empty((K, B, P, ns), dtype=torch.float32, device=b.device)
-    U = torch.empty((B, P, ns), dtype=torch.float32, device=b.device) if want_U else None
-    Grec = Urec = None
-    if record:
-        Grec = torch.empty((K, B, P, ns), dtype=torch.float32, device=b.device)
-        Urec = torch.empty((K, B, P, ns), dtype=torch.float32, device=b.device)
+    ns, dev, L = op.n_store, b.device, _lib.load()
     d = op.dims(B=B, K=K, variant=variant, hyp_rows=H, graph_shared=graphs.shared)
-    L = _lib.load()
-    if path in ("fused", "split") and not graphs.fused_ok:
-        raise ValueError("the fused kernel follows non-ascending adjacency orders only for "
-                         "P <= 8; use path='auto' or 'stepwise'")
-    # small batches (the fused tiles would fill at most half the CUs): the column-split forward
-    split_b = flag_b = 0
-    if path in ("auto", "split") and not record and graphs.fused_ok:
-        split_b = L.dadmm_split_scratch_bytes(ctypes.byref(d))
-        flag_b = L.dadmm_split_flag_bytes(ctypes.byref(d)) if split_b else 0
-    elif record and graphs.fused_ok and (path == "split" or (path == "auto" and train_split)):
-        # training opt-in: the sizes depend on b.device's CU count
-        with torch.cuda.device(b.device):
-            split_b = L.dadmm_split_scratch_bytes(ctypes.byref(d))
-            flag_b = L.dadmm_split_flag_bytes(ctypes.byref(d)) if split_b else 0
-    if path == "split" and split_b == 0:
-        raise ValueError(f"the column-split forward does not serve B={B} P={P} n={ns} "
-                         "(n_pad 128 or 256, P <= 6, m <= 64, ceil(B/16) <= CUs/2)")
-    # one device allocation: [status word | 252 B pad | split epoch words | stepwise scratch
-    # (guard flags first)]; the prologue zeroes the status word, the epoch words and the guard
-    # flags in the same launch as the draws
-    gated = path in ("auto", "stepwise")
-    nbytes = L.dadmm_stepwise_scratch_bytes(ctypes.byref(d)) if gated else 0
-    words = torch.empty(256 + flag_b + max(nbytes, 256), dtype=torch.uint8, device=b.device)
-    status = words[:4].view(torch.int32)
-    sflags = words[256:256 + flag_b]
-    scratch = words[256 + flag_b:]
-    nzero = (256 + flag_b + (_sw_flag_bytes(K) if gated else 0)) // 4
-    if draw:
-        y0, U0, d0 = draw_inits((B, P, op.n), b.device, ns, zero=words, nzero=nzero)
-    else:
-        with torch.cuda.device(b.device):
+    with torch.cuda.device(dev):
+        plan = plan_forward(d, graphs.fused_ok, path=path, record=record, train_split=train_split)
+        b, hyp = b.contiguous().float(), hyp.contiguous().float()
+        Y = torch.empty((K, B, P, ns), dtype=torch.float32, device=dev)
+        U = torch.empty((B, P, ns), dtype=torch.float32, device=dev) if want_U else None
+        rec = tuple(torch.empty_like(Y) for _ in range(2 if record else 0))   # Grec, Urec
+        # one device allocation: [status word | 252 B pad | split epoch words | stepwise scratch
+        # (guard flags first)]; the prologue zeroes the status word, the epoch words and the
+        # guard flags in the same launch as the draws
+        flag_b = plan.split_flag_bytes
+        words = torch.empty(256 + flag_b + max(plan.stepwise_bytes, 256), dtype=torch.uint8,
+                            device=dev)
+        status, scratch = words[:4].view(torch.int32), words[256 + flag_b:]
+        if draw:
+            y0, U0, d0 = draw_inits((B, P, op.n), dev, ns, zero=words, nzero=plan.nzero)
+        else:
+            y0, U0, d0 = (_pad_n(x, ns).contiguous().float() for x in (y0, U0, d0))
             _lib.check("dadmm_prologue", L.dadmm_prologue(
-                0, 0, 0, 1, 1, 0.0, 0.0, None, None, None, _ptr(words), nzero, _stream(b.device)))
-    with torch.cuda.device(b.device):
-        stream = _stream(b.device)
-        fused = path in ("auto", "fused", "split") and graphs.fused_ok
-        if split_b:
-            xbuf = torch.empty(split_b, dtype=torch.uint8, device=b.device)
-            if record:
-                _lib.check("dadmm_forward_split_record", L.dadmm_forward_split_record(
-                    ctypes.byref(d), _ptr(op.workspace), _ptr(b), _ptr(graphs.nbr),
-                    _ptr(graphs.order), _ptr(graphs.deg), _ptr(hyp), _ptr(y0), _ptr(U0), _ptr(d0),
-                    _ptr(Y), _ptr(Grec), _ptr(Urec), _ptr(U), _ptr(status), _ptr(sflags),
-                    _ptr(xbuf), stream))
-            else:
-                _lib.check("dadmm_forward_split", L.dadmm_forward_split(
-                    ctypes.byref(d), _ptr(op.workspace), _ptr(b), _ptr(graphs.nbr),
-                    _ptr(graphs.order), _ptr(graphs.deg), _ptr(hyp), _ptr(y0), _ptr(U0), _ptr(d0),
-                    _ptr(Y), _ptr(U), _ptr(status), _ptr(sflags), _ptr(xbuf), stream))
-        elif fused:
-            if record:
-                rc = L.dadmm_forward_record(
-                    ctypes.byref(d), _ptr(op.workspace), _ptr(b), _ptr(graphs.nbr),
-                    _ptr(graphs.order), _ptr(graphs.deg), _ptr(hyp), _ptr(y0), _ptr(U0), _ptr(d0),
-                    _ptr(Y), _ptr(Grec), _ptr(Urec), _ptr(U), _ptr(status), stream)
-            else:
-                rc = L.dadmm_forward(ctypes.byref(d), _ptr(op.workspace), _ptr(b),
-                                     _ptr(graphs.nbr), _ptr(graphs.order), _ptr(graphs.deg),
-                                     _ptr(hyp), _ptr(y0), _ptr(U0), _ptr(d0), _ptr(Y), _ptr(U),
-                                     _ptr(status), stream)
-            if rc == _lib.DADMM_EUNSUPPORTED and path == "auto":
-                fused = False
-            else:
-                _lib.check("dadmm_forward_record" if record else "dadmm_forward", rc)
-        tiled = path == "tiled" or (path == "auto" and not fused and not record)
-        if record and not fused and path in ("auto", "tiled"):
-            # the streamed single launch records the trajectory (P <= 16, m <= 64); otherwise the
-            # stepwise kernels below record it
-            tb = L.dadmm_tiled_scratch_bytes(ctypes.byref(d))
-            tscratch = torch.empty(max(tb, 256), dtype=torch.uint8, device=b.device)
-            rc = L.dadmm_forward_tiled_record(
-                ctypes.byref(d), _ptr(op.workspace), _ptr(b), _ptr(graphs.vptr), _ptr(graphs.vq),
-                _ptr(graphs.deg), _ptr(hyp), _ptr(y0), _ptr(U0), _ptr(d0), _ptr(Y), _ptr(Grec),
-                _ptr(Urec), _ptr(U), _ptr(status), _ptr(tscratch), stream)
-            if rc == _lib.DADMM_EUNSUPPORTED and path == "auto":
-                tiled = False
-            else:
-                _lib.check("dadmm_forward_tiled_record", rc)
-                tiled = True
-        elif tiled:
-            tb = L.dadmm_tiled_scratch_bytes(ctypes.byref(d))
-            tscratch = torch.empty(max(tb, 256), dtype=torch.uint8, device=b.device)
-            rc = L.dadmm_forward_tiled(
-                ctypes.byref(d), _ptr(op.workspace), _ptr(b), _ptr(graphs.vptr), _ptr(graphs.vq),
-                _ptr(graphs.deg), _ptr(hyp), _ptr(y0), _ptr(U0), _ptr(d0), _ptr(Y), _ptr(U),
-                _ptr(status), _ptr(tscratch), stream)
-            if rc == _lib.DADMM_EUNSUPPORTED and path == "auto":
-                tiled = False
-            else:
-                _lib.check("dadmm_forward_tiled", rc)
-        if gated:
-            gate = _lib.FLAGS_ZEROED | (_lib.GATE_ON if (fused or tiled) else 0)
+                0, 0, 0, 1, 1, 0.0, 0.0, None, None, None, _ptr(words), plan.nzero, _stream(dev)))
+        head = (ctypes.byref(d), _ptr(op.workspace), _ptr(b))
+        tail = (_ptr(graphs.deg), _ptr(hyp), _ptr(y0), _ptr(U0), _ptr(d0), _ptr(Y))
+        a = types.SimpleNamespace(
+            L=L, dp=head[0], plan=plan, device=dev, stream=_stream(dev),
+            ordered=(*head, _ptr(graphs.nbr), _ptr(graphs.order), *tail),     # fused, split
+            visits=(*head, _ptr(graphs.vptr), _ptr(graphs.vq), *tail),        # tiled, stepwise
+            rec=tuple(_ptr(x) for x in rec), U=_ptr(U), status=_ptr(status),
+            sflags=_ptr(words[256:256 + flag_b]))
+        ran = None
+        for name in plan.candidates:
+            fn, rc = _FORWARD_LAUNCHERS[name](a)
+            if rc != _lib.DADMM_EUNSUPPORTED or path != "auto":
+                _lib.check(fn, rc)
+                ran = name
+                break
+        if plan.gated:
+            gate = _lib.FLAGS_ZEROED | (_lib.GATE_ON if ran else 0)
             _lib.check("dadmm_forward_stepwise", L.dadmm_forward_stepwise(
-                ctypes.byref(d), _ptr(op.workspace), _ptr(b), _ptr(graphs.vptr), _ptr(graphs.vq),
-                _ptr(graphs.deg), _ptr(hyp), _ptr(y0), _ptr(U0), _ptr(d0), _ptr(Y), _ptr(U),
-                _ptr(Grec), _ptr(Urec), _ptr(status), gate, _ptr(scratch), stream))
-    traj = Trajectory(Y, Grec, Urec, y0, d0, hyp, variant, fused) if record else None
+                *a.visits, a.U, *(a.rec or (None, None)), a.status, gate, _ptr(scratch), a.stream))
+    traj = Trajectory(Y, *rec, y0, d0, hyp, variant, ran in ("fused", "split")) if record else None
     if ns != op.n:
         Y = Y[..., : op.n]
         U = U[..., : op.n] if U is not None else None
-    if record:
-        return Y, U, status, traj
-    return Y, U, status
+    return (Y, U, status, traj) if record else (Y, U, status)
+
+
+def _split_cols(d, fused_ok, record=False, train_split=False):
+    plan = plan_forward(d, fused_ok, record=record, train_split=train_split)
+    return 64 if "split" in plan.candidates else 0
 
 
 def split_cols(op: PreparedOperator, B: int, K: int, graphs: GraphBatch = None, hyp_rows: int = 1,
                record: bool = False, train_split: bool = False) -> int:
     """The GEMM1 slice width forward_raw's "auto" path uses for this batch: 64 when it runs the
     column-split forward (dadmm_forward_split; with ``record``, dadmm_forward_split_record, which
-    needs ``train_split``), else 0 (the oracle's ``split_cols`` argument)."""
-    if (record and not train_split) or (graphs is not None and not graphs.fused_ok):
-        return 0
+    needs ``train_split``), else 0 (the oracle's ``split_cols`` argument). graphs None: a shared
+    graph the fused kernel follows."""
     shared = graphs.shared if graphs is not None else 1
     d = op.dims(B=B, K=K, hyp_rows=hyp_rows, graph_shared=shared)
-    if record:
-        with torch.cuda.device(op.device):
-            return 64 if _lib.load().dadmm_split_scratch_bytes(ctypes.byref(d)) else 0
-    return 64 if _lib.load().dadmm_split_scratch_bytes(ctypes.byref(d)) else 0
+    with torch.cuda.device(op.device):
+        return _split_cols(d, graphs is None or graphs.fused_ok, record, train_split)
 
 
 class Trajectory:
@@ -296,46 +300,42 @@ def backward_raw(op: PreparedOperator, graphs: GraphBatch, traj: Trajectory,
     if path not in ("auto", "fused", "general"):
         raise ValueError(f"unknown path {path!r}")
     # compute_delta is the sum over its visits (p, q) of (e_p - e_q)(e_p - e_q)^T: symmetric for
-    # ANY adjacency, so every adjoint applies it through the forward's own visit order. The fused
-    # adjoint's shared-graph consensus (consensus_fma) reads one edge multiplier per unordered
-    # pair, i.e. assumes a symmetric adjacency: a directed SHARED graph takes the general adjoint
-    # (its visit lists follow the successor lists); per-sample graphs use the direction-aware
-    # consensus_lane / consensus_ordered in either adjoint.
+    # ANY adjacency, so every adjoint applies it through the forward's own visit order. Only the
+    # fused adjoint's shared-graph consensus (consensus_fma) reads one edge multiplier per
+    # unordered pair: a directed SHARED graph takes the general adjoint (its visit lists follow
+    # the successor lists); per-sample graphs are direction-aware in either adjoint.
     directed_shared = graphs.shared and not getattr(graphs, "symmetric", True)
     K, B, P, ns = traj.Y.shape
     H = int(traj.hyp.shape[1])
     gY = _pad_n(gY.float(), ns).contiguous()
     if tuple(gY.shape) != (K, B, P, ns):
         raise ValueError(f"gY must be [{K},{B},{P},{op.n}], got {tuple(gY.shape)}")
-    d = op.dims(B=B, K=K, variant=traj.variant, hyp_rows=H, graph_shared=graphs.shared)
-    L = _lib.load()
-    dhyp = torch.empty((K, H, 4), dtype=torch.float32, device=gY.device)
     if path == "fused" and directed_shared:
         raise ValueError("the fused adjoint assumes a symmetric shared adjacency; use 'auto' or "
                          "'general' for a directed shared graph")
+    if path == "fused" and not graphs.fused_ok:
+        raise ValueError("the fused adjoint follows non-ascending adjacency orders only "
+                         "for P <= 8; use path='auto' or 'general'")
     use_fused = path == "fused" or (path == "auto" and traj.fused and graphs.fused_ok
                                     and not directed_shared)
-    with torch.cuda.device(gY.device):
-        stream = _stream(gY.device)
+    d = op.dims(B=B, K=K, variant=traj.variant, hyp_rows=H, graph_shared=graphs.shared)
+    L, dp, dev = _lib.load(), ctypes.byref(d), gY.device
+    dhyp = torch.empty((K, H, 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        def launch(fn, g0, g1, scratch):   # nbr / order (fused adjoint) or the visit lists
+            return fn(dp, *(_ptr(t) for t in (
+                op.workspace, g0, g1, graphs.deg, traj.hyp, traj.y0, traj.d0, traj.Y, traj.Grec,
+                traj.Urec, gY, dhyp, scratch)), _stream(dev))
         if use_fused:
-            if not graphs.fused_ok:
-                raise ValueError("the fused adjoint follows non-ascending adjacency orders only "
-                                 "for P <= 8; use path='auto' or 'general'")
-            nbytes = L.dadmm_backward_scratch_bytes(ctypes.byref(d))
-            scratch = torch.empty(max(nbytes, 16) // 4 + 4, dtype=torch.float32, device=gY.device)
-            rc = L.dadmm_backward(ctypes.byref(d), _ptr(op.workspace), _ptr(graphs.nbr),
-                                  _ptr(graphs.order), _ptr(graphs.deg), _ptr(traj.hyp),
-                                  _ptr(traj.y0), _ptr(traj.d0), _ptr(traj.Y), _ptr(traj.Grec),
-                                  _ptr(traj.Urec), _ptr(gY), _ptr(dhyp), _ptr(scratch), stream)
+            nbytes = L.dadmm_backward_scratch_bytes(dp)
+            scratch = torch.empty(max(nbytes, 16) // 4 + 4, dtype=torch.float32, device=dev)
+            rc = launch(L.dadmm_backward, graphs.nbr, graphs.order, scratch)
             if rc != _lib.DADMM_EUNSUPPORTED or path == "fused":
                 _lib.check("dadmm_backward", rc)
                 return dhyp
-        nbytes = L.dadmm_adjoint_scratch_bytes(ctypes.byref(d))
-        scratch = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=gY.device)
-        _lib.check("dadmm_adjoint", L.dadmm_adjoint(
-            ctypes.byref(d), _ptr(op.workspace), _ptr(graphs.vptr), _ptr(graphs.vq),
-            _ptr(graphs.deg), _ptr(traj.hyp), _ptr(traj.y0), _ptr(traj.d0), _ptr(traj.Y),
-            _ptr(traj.Grec), _ptr(traj.Urec), _ptr(gY), _ptr(dhyp), _ptr(scratch), stream))
+        scratch = torch.empty(max(L.dadmm_adjoint_scratch_bytes(dp), 256), dtype=torch.uint8,
+                              device=dev)
+        _lib.check("dadmm_adjoint", launch(L.dadmm_adjoint, graphs.vptr, graphs.vq, scratch))
     return dhyp
 
 
