@@ -182,6 +182,9 @@ void fill_fused(dadmm::FusedArgs& a, const dadmm_dims* d, const void* op, const 
     a.Urec = nullptr;
 }
 
+// which form of the fused inference forward runs where both exist
+constexpr bool FUSED_ROLES_DEFAULT = true;
+
 int forward_impl(const dadmm_dims* d, const void* op, const float* b, const uint64_t* nbr,
                  const uint32_t* nbr_order, const float* deg, const float* hyp, const float* y0,
                  const float* U0, const float* d0, float* Y, float* Grec, float* Urec,
@@ -201,6 +204,15 @@ int forward_impl(const dadmm_dims* d, const void* op, const float* b, const uint
     if (fn == nullptr)
         return fail(DADMM_EUNSUPPORTED, "no fused kernel for P=%d n=%d (n_pad=%d)", d->P, d->n,
                     64 * nt);
+    // the role-split form (dadmm_fused_roles.hip) for the instantiations it covers;
+    // DADMM_FUSED_FORM=rows|roles selects either form (tests of both, A/B timing in one process;
+    // set to anything but "roles" it selects the row-split form)
+    if (!rec) {
+        const char* fenv = getenv("DADMM_FUSED_FORM");
+        const bool roles = fenv != nullptr ? strcmp(fenv, "roles") == 0 : FUSED_ROLES_DEFAULT;
+        dadmm::fused_fn_ptr rfn = roles ? dadmm::find_fused_roles(d->P, nt, graph) : nullptr;
+        if (rfn != nullptr) fn = rfn;
+    }
     dadmm::FusedArgs a;
     fill_fused(a, d, op, b, nbr, nbr_order, deg, hyp, y0, U0, d0, Y, U_out, status);
     a.Grec = Grec;

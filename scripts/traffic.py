@@ -16,7 +16,8 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNEL = "fused_forward_kernel"
+# the headline launch: the row-split form or the role-split form
+KERNEL = os.environ.get("DADMM_TRAFFIC_KERNEL", "fused_roles_kernel")
 
 
 def per_launch(pmc_dir, counter):
