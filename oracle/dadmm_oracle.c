@@ -274,6 +274,18 @@ int oracle_forward_f32_rec(int B, int P, int m, int n, int K, int variant, int h
                             y0, U0, d0, Y, U_out, status, Grec, Urec, 0, 0);
 }
 
+/* oracle_forward_f32_rec with GEMM1 in the column-split order (the recording split forward). */
+int oracle_forward_f32_split_rec(int B, int P, int m, int n, int K, int variant, int hyp_mode, int H,
+                                 const float* A, const float* b, const int32_t* nbr_ptr,
+                                 const int32_t* nbr_idx, const float* deg, const float* hyp,
+                                 const float* y0, const float* U0, const float* d0, float* Y,
+                                 float* U_out, int32_t* status, float* Grec, float* Urec,
+                                 int split_cols) {
+    if (split_cols < 0 || (split_cols & 15)) return -1;
+    return forward_f32_impl(B, P, m, n, K, variant, hyp_mode, H, A, b, nbr_ptr, nbr_idx, deg, hyp,
+                            y0, U0, d0, Y, U_out, status, Grec, Urec, 0, split_cols);
+}
+
 /* The GNN model's recurrence in the order of the per-iteration HIP path (dadmm_gnn.hip): gradient
  * ((((AtAy - Atb) + sign*tau) + U*deg) + delta*rho) with AtAy = A^T (A y) and Atb = A^T b as
  * separate fma chains. Usually hyp_mode 1 (the hypernetwork's per-sample [K][B][4][H]). */

@@ -49,6 +49,8 @@ def lib() -> ctypes.CDLL:
         L.oracle_forward_f32_rec.restype = ctypes.c_int
         L.oracle_forward_f32_rec.argtypes = [i, i, i, i, i, i, i, i] + [fp] * 14
         L.oracle_forward_f32_split.argtypes = [i, i, i, i, i, i, i, i] + [fp] * 12 + [i]
+        L.oracle_forward_f32_split_rec.restype = ctypes.c_int
+        L.oracle_forward_f32_split_rec.argtypes = [i, i, i, i, i, i, i, i] + [fp] * 14 + [i]
         L.oracle_abi_version.restype = ctypes.c_int
         L.oracle_set_threads.restype = ctypes.c_int
         L.oracle_set_threads.argtypes = [i]
@@ -151,14 +153,19 @@ def forward_f32(A, b, graph_list, hyp, y0, U0, d0, variant=0, hyp_mode=0, split_
                 hyp_mode)
 
 
-def forward_f32_rec(A, b, graph_list, hyp, y0, U0, d0, variant=0, hyp_mode=0):
+def forward_f32_rec(A, b, graph_list, hyp, y0, U0, d0, variant=0, hyp_mode=0, split_cols=0):
     """forward_f32 that also records the adjoint's trajectory.
 
     Returns (Y, U_K, status, Grec, Urec): Grec[k] = the gradient of iteration k before its clamp
-    (unfolded_DLASSO.py:73-77), Urec[k] = U_k entering iteration k; both [K,B,P,n] float32."""
+    (unfolded_DLASSO.py:73-77), Urec[k] = U_k entering iteration k; both [K,B,P,n] float32.
+    ``split_cols`` > 0: GEMM1 in the column-split order, as forward_f32 takes it."""
     rec = [None, None]
-    Y, U, st = _run(lib().oracle_forward_f32_rec, np.float32, A, b, graph_list, hyp, y0, U0, d0,
-                    variant, hyp_mode, rec)
+    if split_cols:
+        Y, U, st = _run(lib().oracle_forward_f32_split_rec, np.float32, A, b, graph_list, hyp, y0,
+                        U0, d0, variant, hyp_mode, rec, tail=(int(split_cols),))
+    else:
+        Y, U, st = _run(lib().oracle_forward_f32_rec, np.float32, A, b, graph_list, hyp, y0, U0, d0,
+                        variant, hyp_mode, rec)
     return Y, U, st, rec[0], rec[1]
 
 
@@ -238,7 +245,7 @@ def laplacians(graph_list, P):
     return L, deg
 
 
-def backward_np64(A, graph_list, hyp, y0, d0, Y, Grec, Urec, gY, variant=0):
+def backward_np64(A, graph_list, hyp, y0, d0, Y, Grec, Urec, gY, variant=0, dtype=np.float64):
     """d(sum_k <gY[k], Y[k]>) / d hyp  ->  [K, H, 4] float64, in reverse mode along a recorded
     trajectory (Y, Grec, Urec as forward_f32_rec / the HIP recording path return them).
 
@@ -258,56 +265,61 @@ def backward_np64(A, graph_list, hyp, y0, d0, Y, Grec, Urec, gY, variant=0):
     consensus in float64, so a float32 trajectory can differ from the kernels' masks only where
     |w| or |2Ly| lies within rounding of its clip bound. Sums run over the batch and n; for
     H = 1 ('same' mode) also over the agents. No guard handling: finite trajectories only.
+
+    ``dtype`` np.float32: the same arithmetic in float32 (numpy's pairwise sums; the masks then
+    come from float32 values of w and 2Ly). Its distance from the float64 result along one
+    trajectory is that trajectory's fp32 rounding scale for an adjoint.
     """
-    A = np.asarray(A, np.float64).reshape(np.shape(A)[-3:])
+    dt = np.dtype(dtype).type
+    A = np.asarray(A, dt).reshape(np.shape(A)[-3:])
     P, m, n = A.shape
     K, B = Y.shape[0], Y.shape[1]
     tdt = np.asarray(Y).dtype
     AtA = np.einsum("pri,prj->pij", A, A)
-    L, deg = laplacians(graph_list, P)
+    L, deg = (v.astype(dt) for v in laplacians(graph_list, P))
     hyp = np.asarray(hyp)
     H = hyp.shape[1]
-    Yd = np.asarray(Y, np.float64).reshape(K, B, P, n)
-    y0d = np.asarray(y0, np.float64).reshape(B, P, n)
-    d0d = np.asarray(d0, np.float64).reshape(B, P, n)
-    gY = np.asarray(gY, np.float64).reshape(K, B, P, n)
-    dh = np.zeros((K, P, 4))
-    yb = np.zeros((B, P, n))
-    Ub = np.zeros((B, P, n))
-    db = np.zeros((B, P, n))
+    Yd = np.asarray(Y, dt).reshape(K, B, P, n)
+    y0d = np.asarray(y0, dt).reshape(B, P, n)
+    d0d = np.asarray(d0, dt).reshape(B, P, n)
+    gY = np.asarray(gY, dt).reshape(K, B, P, n)
+    dh = np.zeros((K, P, 4), dt)
+    yb = np.zeros((B, P, n), dt)
+    Ub = np.zeros((B, P, n), dt)
+    db = np.zeros((B, P, n), dt)
 
     def cons(x):
-        return 2.0 * np.einsum("bpq,bqi->bpi", L, x)
+        return dt(2.0) * np.einsum("bpq,bqi->bpi", L, x)
 
     for k in reversed(range(K)):
         hk = np.broadcast_to(hyp[k], (P, 4))
-        al, ta, rh, et = (hk[:, c].astype(np.float64)[None, :, None] for c in range(4))
-        gclip = max(1.0, 30.0 - k) if variant == 0 else 10.0
-        vclip = max(10.0, 200.0 - 3 * k) if variant == 0 else 100.0
+        al, ta, rh, et = (hk[:, c].astype(dt)[None, :, None] for c in range(4))
+        gclip = dt(max(1.0, 30.0 - k) if variant == 0 else 10.0)
+        vclip = dt(max(10.0, 200.0 - 3 * k) if variant == 0 else 100.0)
         y1 = Yd[k]
         yk = Yd[k - 1] if k > 0 else y0d
         d1 = cons(y1)
         md1 = None
         if variant != 0:
-            md1 = np.abs(d1) <= 20.0
-            d1 = np.clip(d1, -20.0, 20.0)
+            md1 = np.abs(d1) <= dt(20.0)
+            d1 = np.clip(d1, dt(-20.0), dt(20.0))
         if k > 0:
             dk = cons(yk)
             if variant != 0:
-                dk = np.clip(dk, -20.0, 20.0)
+                dk = np.clip(dk, dt(-20.0), dt(20.0))
         else:
             dk = d0d
         yb = yb + gY[k]
-        w = np.asarray(Urec[k], np.float64) + d1 * et
+        w = np.asarray(Urec[k], dt) + d1 * et
         wb = Ub * (np.abs(w) <= vclip)
         dh[k, :, 3] += (wb * d1).sum(axis=(0, 2))
         d1b = db + wb * et
         if md1 is not None:
             d1b = d1b * md1
         yb = yb + cons(d1b)
-        gr = np.asarray(Grec[k], np.float64)
+        gr = np.asarray(Grec[k], dt)
         g = np.clip(gr, -gclip, gclip)
-        z = (np.asarray(yk, tdt) - hk[:, 0].astype(tdt)[None, :, None] * g.astype(tdt)).astype(np.float64)
+        z = (np.asarray(yk, tdt) - hk[:, 0].astype(tdt)[None, :, None] * g.astype(tdt)).astype(dt)
         zb = yb * (np.abs(z) <= vclip)
         dh[k, :, 0] += (-zb * g).sum(axis=(0, 2))
         grb = -al * zb * (np.abs(gr) <= gclip)

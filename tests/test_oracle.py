@@ -295,15 +295,23 @@ def _digraph(P, seed):
     return G
 
 
-@pytest.mark.parametrize("variant,H,per_sample,directed", [(0, 5, False, False), (0, 1, False, False),
-                                                           (1, 5, True, False), (1, 1, True, False),
-                                                           (0, 5, False, True), (1, 5, True, True)])
-def test_adjoint_matches_torch_autograd_of_the_reference_ops(variant, H, per_sample, directed):
+_ADJ = [(0, 5, False, False), (0, 1, False, False), (1, 5, True, False), (1, 1, True, False),
+        (0, 5, False, True), (1, 5, True, True)]
+# ladder inputs (tests/saturation.py: vclip on y and U, the delta clamp and sign(0) all active);
+# the last entry is the ladder's top
+_ADJ_LADDER = [(0, 5, False, False, 150.0), (0, 1, True, False, 150.0), (1, 5, True, False, 400.0),
+               (1, 1, False, False, 400.0)]
+
+
+@pytest.mark.parametrize("variant,H,per_sample,directed,ladder", [
+    *(pytest.param(*c, 0, id="-".join(str(v) for v in c)) for c in _ADJ),
+    *(pytest.param(*c, id="-".join(str(v) for v in c[:4]) + "-ladder") for c in _ADJ_LADDER)])
+def test_adjoint_matches_torch_autograd_of_the_reference_ops(variant, H, per_sample, directed, ladder):
     """backward_np64 == torch.autograd.grad through the reference's op sequence (fp64 replay,
     unfolded_DLASSO.py:53-107 + compute_delta's edge loop), on the same trajectory; directed
-    graphs (successor lists) too."""
+    graphs (successor lists) too; and on ladder inputs, where every clamp's mask is mixed."""
     import torch
-    P, m, n, B, K = 5, 16, 48, 3, 12
+    P, m, n, B, K = (5, 16, 48, 3, 12) if not ladder else (5, 16, 48, 10, 4)
     A, b, _ = O.make_problem(P, m, n, B, seed=31)
     if directed:
         graphs = ([_digraph(P, 60 + s) for s in range(B)] if per_sample else [_digraph(P, 7)] * B)
@@ -314,8 +322,15 @@ def test_adjoint_matches_torch_autograd_of_the_reference_ops(variant, H, per_sam
     y0, U0, d0 = _inits(B, P, n, seed=5)
     param = TRAINED[:K, :P] if H == P else TRAINED[:K, :1]
     hyp = O.hyp_table(param, MAXP)
+    if ladder:
+        import saturation
+        y0, U0, d0 = saturation.ladder_inits(B, P, n, 5, ladder)
+        hyp = saturation.ladder_hyp(K, H, 5)
     ht = torch.tensor(hyp, dtype=torch.float64, requires_grad=True)
-    Y, Gr, Ur, _ = ref_torch.forward_autograd(A, b, graphs, ht, y0, U0, d0, variant=variant)
+    Y, Gr, Ur, U_K = ref_torch.forward_autograd(A, b, graphs, ht, y0, U0, d0, variant=variant)
+    if ladder:
+        saturation.assert_engaged(variant, hyp, y0, Y.detach().numpy(), U_K.numpy(), Gr.numpy(),
+                                  Ur.numpy(), graphs)
     gY = torch.randn(Y.shape, dtype=torch.float64, generator=torch.Generator().manual_seed(3))
     want, = torch.autograd.grad((Y * gY).sum(), ht)
     got = O.backward_np64(A, graphs, hyp, y0, d0, Y.detach().numpy(), Gr.numpy(), Ur.numpy(),
