@@ -205,12 +205,14 @@ int forward_impl(const dadmm_dims* d, const void* op, const float* b, const uint
         return fail(DADMM_EUNSUPPORTED, "no fused kernel for P=%d n=%d (n_pad=%d)", d->P, d->n,
                     64 * nt);
     // the role-split form (dadmm_fused_roles.hip) for the instantiations it covers;
-    // DADMM_FUSED_FORM=rows|roles selects either form (tests of both, A/B timing in one process;
-    // set to anything but "roles" it selects the row-split form)
+    // DADMM_FUSED_FORM=rows|roles|roles-stream selects a form (tests of all, A/B timing in one
+    // process): "roles" holds one agent's GEMM1 operand in registers, "roles-stream" streams every
+    // fragment; set to anything else it selects the row-split form
     if (!rec) {
         const char* fenv = getenv("DADMM_FUSED_FORM");
-        const bool roles = fenv != nullptr ? strcmp(fenv, "roles") == 0 : FUSED_ROLES_DEFAULT;
-        dadmm::fused_fn_ptr rfn = roles ? dadmm::find_fused_roles(d->P, nt, graph) : nullptr;
+        const bool stream = fenv != nullptr && strcmp(fenv, "roles-stream") == 0;
+        const bool roles = fenv != nullptr ? stream || strcmp(fenv, "roles") == 0 : FUSED_ROLES_DEFAULT;
+        dadmm::fused_fn_ptr rfn = roles ? dadmm::find_fused_roles(d->P, nt, graph, !stream) : nullptr;
         if (rfn != nullptr) fn = rfn;
     }
     dadmm::FusedArgs a;

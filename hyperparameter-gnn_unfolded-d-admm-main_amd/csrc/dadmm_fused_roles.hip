@@ -12,7 +12,10 @@
 //                                    Glds[p & 1];
 //     A / A^T fragments stream from L2 through ONE compile-time-indexed register ring that runs
 //     through the whole iteration (GEMM2 of agents 0..P-1, then GEMM1 of the next iteration) and
-//     wraps into the next one: RD fragments of lead, no LDS ring, no LDS-DMA;
+//     wraps into the next one: RD fragments of lead, no LDS ring, no LDS-DMA. With RES = 1 the
+//     GEMM1 operand of one agent (RA: rows 16 w..16 w + 15 of A_RA, 64 VGPRs the kernel's
+//     allocation leaves this role anyway) is loaded once per launch and stays in registers for all
+//     K iterations; the stream carries the other agents only;
 //   * waves 4-7 (their SIMD partners) hold U and delta (wave u: n-tiles 4u..4u+3 of every agent,
 //     16 rows per lane and agent) and do everything else: the gradient assembly, clamps and primal
 //     update from Glds / Ylds, the Y[k] store, the consensus and the dual update, the input and
@@ -23,6 +26,8 @@
 //   stage P            matrix: GEMM1(k+1), agents < G1A  update: primal update of agent P - 1
 //   stage P + 1        matrix: GEMM1(k+1), the others    update: consensus and dual update
 // (agent P - 1's y_{k+1} is complete only after stage P, so it is always in the second group).
+// The resident agent's GEMM1 chain runs in its group's stage like the others, interleaved with
+// them step by step: same operands, same order, same seed, so the same bits.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,7 +40,7 @@
 
 namespace dadmm {
 
-template <int P>
+template <int P, int RES>
 struct Roles {
     static constexpr int NP = 256;              // padded n (NT = 4)
     static constexpr int NB = NP / 16;          // 16-row n-tiles
@@ -43,13 +48,26 @@ struct Roles {
     static constexpr int YS = NP + 8;           // LDS row strides (floats), 8 mod 64: see dadmm_fused.hip
     static constexpr int RS = MP + 8;
     static constexpr int GS = NP + 8;
-    // operand ring depth (fragments of 4 VGPRs; must divide 16 P). At P = 5: 20 measured 1 % under
-    // 16 at the headline shape; 40 spills beside the update role's 227 registers
-    static constexpr int RD = P == 5 ? 20 : 16;
-    static constexpr int NF = 32 * P;           // fragments per wave and iteration
+    // operand ring depth (fragments of 4 VGPRs; must divide 16 P and NF). Streamed only, at P = 5:
+    // 20 measured 1 % under 16 at the headline shape; 40 spills beside the update role's 227
+    // registers. With the resident block NF = 32 P - 16, so 16 for every P
+    static constexpr int RD = (P == 5 && RES == 0) ? 20 : 16;
     static constexpr int G1A = (P - 1) / 2;     // GEMM1 agents of stage P (agents 0..G1A-1)
     static constexpr int G1B = P - G1A;         // GEMM1 agents of stage P + 1
+    // the resident agent (RES = 1). Agent 0 puts the block in stage P where there is one (P >= 3):
+    // at P = 5 that stage then streams agent 1 alone, 16 fragments, which the ring already holds
+    // when the stage begins, and stage P + 1 streams its three agents beside the consensus as
+    // before. Measured at the headline shape against the streamed form: agent 0
+    // -0.031 ms; agent G1A (two streamed agents in either stage) and agent P - 1 -0.003 ms
+    static constexpr int RA = 0;
+    static constexpr int SA = G1A - (RES && RA < G1A ? 1 : 0);    // streamed GEMM1 agents of stage P
+    static constexpr int SB = G1B - (RES && RA >= G1A ? 1 : 0);   // ... of stage P + 1
+    static constexpr int NF = 32 * P - 16 * RES;                  // fragments per wave and iteration
     static constexpr int LDS_FLOATS = P * BT * YS + P * BT * RS + 2 * BT * GS;
+    static_assert(RES == 0 || RES == 1, "one resident block or none");
+    static_assert(RA >= 0 && RA < P, "the resident agent");
+    static_assert(NF == 16 * (P + SA + SB), "the stream: GEMM2 of every agent, GEMM1 of the streamed ones");
+    static_assert(NF % RD == 0, "ring slots must line up where the stream wraps");
     static_assert((16 * P) % RD == 0, "ring slots must line up at the GEMM2 / GEMM1 boundary");
 };
 
@@ -67,11 +85,11 @@ __device__ __forceinline__ void stage_barrier() {
     pin();
 }
 
-template <int P>
+template <int P, int RES>
 __device__ __forceinline__ void roles_matrix(const FusedArgs& a, float* __restrict__ lds, const int w) {
-    using C = Roles<P>;
+    using C = Roles<P, RES>;
     constexpr int NP = C::NP, NB = C::NB, MP = C::MP, YS = C::YS, RS = C::RS, GS = C::GS;
-    constexpr int RD = C::RD, NF = C::NF, G1A = C::G1A, G1B = C::G1B;
+    constexpr int RD = C::RD, NF = C::NF, G1A = C::G1A, G1B = C::G1B, RA = C::RA, SA = C::SA, SB = C::SB;
     float* __restrict__ Ylds = lds;                  // [P][BT][YS]   y_k, n contiguous
     float* __restrict__ Rlds = lds + P * BT * YS;    // [P][BT][RS]   A y - b, m contiguous
     float* __restrict__ Glds = Rlds + P * BT * RS;   // [2][BT][GS]   G_p, n contiguous (agent parity)
@@ -107,7 +125,8 @@ __device__ __forceinline__ void roles_matrix(const FusedArgs& a, float* __restri
 
     // The iteration's fragment stream, in consumption order:
     //   i <  16 P:  GEMM2, agent i / 16, m-block (i % 16) / 4, n-tile 4 w + i % 4;
-    //   then GEMM1 of agents 0..G1A-1 (step t, agent: t * G1A + agent), then of agents G1A..P-1.
+    //   then GEMM1 of the streamed agents of 0..G1A-1 (step t, the group's c-th streamed agent:
+    //   t * SA + c), then of those of G1A..P-1 (t * SB + c); the resident agent has no fragment here.
     // Fragment i lives in ring slot i % RD; fragment i + RD is issued right behind the MFMAs that
     // read fragment i. soffset carries the agent's (and the n-tile's) block, the immediate the
     // 64-B step.
@@ -118,21 +137,36 @@ __device__ __forceinline__ void roles_matrix(const FusedArgs& a, float* __restri
             ring[i % RD] = bload4(rAt, vAt + 64 * t, (uint32_t)((p * NP + 16 * tt) * MP * 4));
         } else {
             int ii = i - 16 * P, p, t;
-            if (ii < 16 * G1A) {
-                t = ii / (G1A > 0 ? G1A : 1);
-                p = ii % (G1A > 0 ? G1A : 1);
+            if (ii < 16 * SA) {
+                t = ii / (SA > 0 ? SA : 1);
+                p = ii % (SA > 0 ? SA : 1);
+                if (RES && RA < G1A && p >= RA) ++p;
             } else {
-                ii -= 16 * G1A;
-                t = ii / G1B;
-                p = G1A + ii % G1B;
+                ii -= 16 * SA;
+                t = ii / (SB > 0 ? SB : 1);
+                p = G1A + ii % (SB > 0 ? SB : 1);
+                if (RES && RA >= G1A && p >= RA) ++p;
             }
             ring[i % RD] = bload4(rA, vA + 64 * t, (uint32_t)(p * MP * NP * 4));
         }
     };
 
-    // GEMM1 of agents P0..P0+CNT-1 (interleaved chains), fragments from stream position BASE
+    // the resident block: agent RA's 16 GEMM1 fragments of this wave, at the offsets the ring would
+    // load them from. Loaded here, once per launch, and read by every iteration's GEMM1
+    f32x4 res[RES ? NB : 1];
+    if constexpr (RES) {
+#pragma unroll
+        for (int t = 0; t < NB; ++t) res[t] = bload4(rA, voffA + 64 * t, (uint32_t)(RA * MP * NP * 4));
+    }
+
+    // GEMM1 of agents P0..P0+CNT-1 (interleaved chains); the streamed ones' fragments from stream
+    // position BASE, the resident agent's from res
     auto gemm1 = [&](auto p0_, auto cnt_, auto base_) {
         constexpr int P0 = decltype(p0_)::value, CNT = decltype(cnt_)::value, BASE = decltype(base_)::value;
+        constexpr bool HAS = RES && RA >= P0 && RA < P0 + CNT;   // the resident agent is in this group
+        constexpr int S = CNT - (HAS ? 1 : 0);                   // streamed chains
+        // chain i's place among the group's streamed chains
+        auto sidx = [](int i) { return i - ((HAS && P0 + i > RA) ? 1 : 0); };
         if constexpr (CNT > 0) {
             f32x4 acc[CNT];
             f32x4 bring[2][CNT];
@@ -151,10 +185,12 @@ __device__ __forceinline__ void roles_matrix(const FusedArgs& a, float* __restri
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
 #pragma unroll
-                    for (int i = 0; i < CNT; ++i)
-                        acc[i] = mfma4(ring[(BASE + t * CNT + i) % RD][r], bring[t & 1][i][r], acc[i]);
+                    for (int i = 0; i < CNT; ++i) {
+                        const float av = (HAS && P0 + i == RA) ? res[t][r] : ring[(BASE + t * S + sidx(i)) % RD][r];
+                        acc[i] = mfma4(av, bring[t & 1][i][r], acc[i]);
+                    }
 #pragma unroll
-                for (int i = 0; i < CNT; ++i) frag_load((BASE + t * CNT + i + RD) % NF);
+                for (int i = 0; i < S; ++i) frag_load((BASE + t * S + i + RD) % NF);
                 pin();
             }
 #pragma unroll
@@ -200,13 +236,14 @@ __device__ __forceinline__ void roles_matrix(const FusedArgs& a, float* __restri
         }
     };
 
-    // the ring's first RD fragments: the head of GEMM1
+    // the ring's first RD fragments: the head of GEMM1, running on into GEMM2 where fewer than RD
+    // GEMM1 fragments are streamed
 #pragma unroll
-    for (int i = 0; i < RD; ++i) frag_load(16 * P + i);
+    for (int i = 0; i < RD; ++i) frag_load((16 * P + i) % NF);
     __syncthreads();                     // y_0 in Ylds
 
     gemm1(ic<0>{}, ic<G1A>{}, ic<16 * P>{});
-    gemm1(ic<G1A>{}, ic<G1B>{}, ic<16 * P + 16 * G1A>{});
+    gemm1(ic<G1A>{}, ic<G1B>{}, ic<16 * P + 16 * SA>{});
     stage_barrier();                     // R(0)
 
     for (int k = 0; k < a.K; ++k) {
@@ -217,7 +254,7 @@ __device__ __forceinline__ void roles_matrix(const FusedArgs& a, float* __restri
         if (k + 1 < a.K) {
             gemm1(ic<0>{}, ic<G1A>{}, ic<16 * P>{});
             stage_barrier();             // stage P
-            gemm1(ic<G1A>{}, ic<G1B>{}, ic<16 * P + 16 * G1A>{});
+            gemm1(ic<G1A>{}, ic<G1B>{}, ic<16 * P + 16 * SA>{});
             stage_barrier();             // stage P + 1
         } else {
             __syncthreads();
@@ -229,7 +266,7 @@ __device__ __forceinline__ void roles_matrix(const FusedArgs& a, float* __restri
 // ---- update role: waves 4-7 (u = wave - 4) --------------------------------------------------------
 template <int P>
 __device__ __forceinline__ void roles_update(const FusedArgs& a, float* __restrict__ lds, const int u) {
-    using C = Roles<P>;
+    using C = Roles<P, 0>;               // (the LDS layout: the same with and without the resident block)
     constexpr int NP = C::NP, MP = C::MP, YS = C::YS, RS = C::RS, GS = C::GS;
     constexpr int T2 = 4;                // n-tiles of this wave: 4 u + tt
     constexpr int E = T2 * 4;            // state elements per lane per agent
@@ -441,33 +478,34 @@ __device__ __forceinline__ void roles_update(const FusedArgs& a, float* __restri
     }
 }
 
-template <int P>
+template <int P, int RES>
 __global__ __launch_bounds__(FUSED_WAVES * 64) void fused_roles_kernel(FusedArgs a) {
-    __shared__ __attribute__((aligned(16))) float lds[Roles<P>::LDS_FLOATS];
+    __shared__ __attribute__((aligned(16))) float lds[Roles<P, RES>::LDS_FLOATS];
     static_assert(FUSED_WAVES == 8, "one matrix wave and one update wave per SIMD");
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave id, in an SGPR
     if (w < 4)
-        roles_matrix<P>(a, lds, w);
+        roles_matrix<P, RES>(a, lds, w);
     else
         roles_update<P>(a, lds, w - 4);
 }
 
-template <int P>
+template <int P, int RES>
 static hipError_t launch_roles(const FusedArgs& a, hipStream_t stream) {
     const int grid = (a.B + BT - 1) / BT;
-    hipLaunchKernelGGL((fused_roles_kernel<P>), dim3(grid), dim3(FUSED_WAVES * 64), 0, stream, a);
+    hipLaunchKernelGGL((fused_roles_kernel<P, RES>), dim3(grid), dim3(FUSED_WAVES * 64), 0, stream, a);
     return hipGetLastError();
 }
 
 // Instantiated shapes: P = 1..5, n_pad = 256, one shared graph, no recording; nullptr otherwise.
-fused_fn_ptr find_fused_roles(int P, int nt, int graph) {
+// resident: with one agent's GEMM1 operand held in registers (RES = 1), or every fragment streamed.
+fused_fn_ptr find_fused_roles(int P, int nt, int graph, bool resident) {
     if (nt != 4 || graph != GRAPH_SHARED) return nullptr;
     switch (P) {
-        case 1: return &launch_roles<1>;
-        case 2: return &launch_roles<2>;
-        case 3: return &launch_roles<3>;
-        case 4: return &launch_roles<4>;
-        case 5: return &launch_roles<5>;
+        case 1: return resident ? &launch_roles<1, 1> : &launch_roles<1, 0>;
+        case 2: return resident ? &launch_roles<2, 1> : &launch_roles<2, 0>;
+        case 3: return resident ? &launch_roles<3, 1> : &launch_roles<3, 0>;
+        case 4: return resident ? &launch_roles<4, 1> : &launch_roles<4, 0>;
+        case 5: return resident ? &launch_roles<5, 1> : &launch_roles<5, 0>;
         default: return nullptr;
     }
 }

@@ -42,8 +42,9 @@ fused_fn_ptr find_fused(int P, int nt, int graph);
 // Same shapes, recording the adjoint's trajectory (a.Grec / a.Urec must be set).
 fused_fn_ptr find_fused_rec(int P, int nt, int graph);
 // The role-split form of the inference forward (dadmm_fused_roles.hip): P = 1..5, nt = 4,
-// GRAPH_SHARED; nullptr otherwise.
-fused_fn_ptr find_fused_roles(int P, int nt, int graph);
+// GRAPH_SHARED; nullptr otherwise. resident: one agent's GEMM1 operand held in registers for the
+// whole launch (the default form), or every operand fragment streamed.
+fused_fn_ptr find_fused_roles(int P, int nt, int graph, bool resident);
 
 // ---- the column-split forward for small batches (dadmm_split.hip) ------------------------------
 constexpr int SPLIT_COLS = 64;   // columns of n_pad per slice (one workgroup each)
