@@ -1,11 +1,14 @@
 // dadmm_device.h — the device-only primitives of the kernel translation units, each stated once:
 // vector / resource / address-space types, MFMA and buffer-memory wrappers, the clamps and guards,
-// the compiler-opacity helpers, the guard-flag atomics, the XCD swizzle, the wave reductions and
-// the reference's per-iteration clip schedule. Everything is __forceinline__: no symbol is emitted.
+// the compiler-opacity helpers, the guard-flag atomics, the XCD swizzle, the wave reductions, the
+// reference's per-iteration clip schedule and the element update it feeds. Everything is
+// __forceinline__: no symbol is emitted.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "dadmm_internal.h"
 
 namespace dadmm {
 
@@ -118,6 +121,62 @@ __device__ __forceinline__ void iter_clips(int variant, int k, float& gclip, flo
 // GNN variant only: delta = clamp(delta, -20, 20) (gnn_dlasso_models_progressive.py:229)
 constexpr float GNN_DELTA_LIMIT = 20.0f;
 
+// ---- the D-ADMM element update -------------------------------------------------------------------
+// One iteration's arithmetic on one element of (y, U, delta), the single statement of it on the
+// device side for every forward kernel (like iter_clips, restated independently by the oracle and
+// dadmm_cpu.py). Each kernel family keeps its clamp: MED3 = mclamp (the on-chip forwards: fused,
+// role-split, column-split), MINMAX = tclamp (tiled, stream), NANPROP = clamp_t (the guarded
+// stepwise and GNN paths). The guards (NaN / finite checks), the recording of the trajectory and
+// the masking of lanes differ by design and stay with the kernels.
+enum class Clamp { MED3, MINMAX, NANPROP };
+template <Clamp C>
+__device__ __forceinline__ float clampf(float x, float lo, float hi) {
+    if constexpr (C == Clamp::MED3) return mclamp(x, lo, hi);
+    else if constexpr (C == Clamp::MINMAX) return tclamp(x, lo, hi);
+    else return clamp_t(x, lo, hi);
+}
+// grad = (AtAy - Atb) + sign(y)*tau + U*deg + delta*rho, left to right, one rounding per operation
+// (unfolded_DLASSO.py:73-77); g = the factored gradient A^T (A y - b)
+__device__ __forceinline__ float grad_assemble(float g, float y, float u, float d, float tau, float deg,
+                                               float rho) {
+    g = g + sign_times(y, tau);
+    g = g + u * deg;
+    return g + d * rho;
+}
+template <Clamp C>
+__device__ __forceinline__ float grad_clamp(float gr, float gclip) {                 // :80-81
+    return clampf<C>(gr, -gclip, gclip);
+}
+// y_next = clamp(y - alpha * grad, +-vclip), grad already clamped (:89, :92-93)
+template <Clamp C>
+__device__ __forceinline__ float primal_y(float y, float alpha, float g_clamped, float vclip) {
+    return clampf<C>(y - alpha * g_clamped, -vclip, vclip);
+}
+// the gradient clamp and the primal update in one place (:80-93)
+template <Clamp C>
+__device__ __forceinline__ float primal_elem(float y, float gr, float alpha, float gclip, float vclip) {
+    return primal_y<C>(y, alpha, grad_clamp<C>(gr, gclip), vclip);
+}
+// GNN variant: delta = clamp(delta, +-dlim) (gnn_dlasso_models_progressive.py:229); the unfolded
+// variant passes dlim = +inf (a no-op on finite delta) or skips the call
+template <Clamp C>
+__device__ __forceinline__ float delta_clamp(float cons, float dlim) {
+    return clampf<C>(cons, -dlim, dlim);
+}
+// U_next = clamp(U + delta * eta, +-vclip) (:98-99)
+template <Clamp C>
+__device__ __forceinline__ float dual_u(float u, float d, float eta, float vclip) {
+    return clampf<C>(u + d * eta, -vclip, vclip);
+}
+// the dual update from the consensus sum cons = 2 L y (:95-99)
+template <Clamp C>
+__device__ __forceinline__ void dual_elem(float cons, float eta, float dlim, float vclip, float& U,
+                                          float& D) {
+    const float d = delta_clamp<C>(cons, dlim);
+    U = dual_u<C>(U, d, eta, vclip);
+    D = d;
+}
+
 // ---- compiler opacity --------------------------------------------------------------------------
 // A per-iteration opaque copy of a loop-invariant offset: keeps `base + constant` inside the loop
 // so instruction selection folds the constant into the load's immediate offset instead of LICM
@@ -143,6 +202,14 @@ __device__ __forceinline__ int flag_ld(const int32_t* f) {
 __device__ __forceinline__ void flag_or(int32_t* f, bool v) {
     if (__ballot(v) != 0 && (threadIdx.x & 63) == 0)
         __hip_atomic_fetch_or(f, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---- the hyper-parameter table of the on-chip forwards (fused, role-split, column-split) --------
+// seq_hyp(k) row p: (alpha, tau, rho, eta), kernel-uniform scalars through the scalar cache
+__device__ __forceinline__ void load_hyp_row(const FusedArgs& a, int k, int p, float& al, float& ta,
+                                             float& rh, float& et) {
+    const cfloat* hp = (const cfloat*)a.hyp + ((size_t)k * a.hyp_rows + (a.hyp_rows == 1 ? 0 : p)) * 4;
+    al = hp[0]; ta = hp[1]; rh = hp[2]; et = hp[3];
 }
 
 // XCD-aware block order: the dispatcher deals blocks round-robin over the 8 XCDs, each with its

@@ -206,7 +206,7 @@ __device__ __forceinline__ void fused_body(const FusedArgs& a, float* __restrict
         for (int p = 0; p < P; ++p)
 #pragma unroll
             for (int e = 0; e < E; ++e) bad_u |= !finitef(U[p][e]);
-        status |= (bad_y ? 1u : 0u) | (bad_u ? 2u : 0u);
+        status |= (bad_y ? DADMM_STATUS_Y_NONFINITE : 0) | (bad_u ? DADMM_STATUS_U_NONFINITE : 0);
     }
 
     // A non-finite hyper-parameter makes y_next NaN (reference guard :102): flag it once for the
@@ -215,11 +215,11 @@ __device__ __forceinline__ void fused_body(const FusedArgs& a, float* __restrict
         bool bad_h = false;
         const int nh = a.K * a.hyp_rows * 4;
         for (int i = threadIdx.x; i < nh; i += WAVES * 64) bad_h |= !finitef(a.hyp[i]);
-        status |= bad_h ? 8u : 0u;
+        status |= bad_h ? DADMM_STATUS_YNEXT_NAN : 0;
     }
     // the shared graph's edges as float 0/1 multipliers, mf[a][b] = (b in N(a)), a < b (uniform);
     // consensus_fma needs a symmetric adjacency: an asymmetric one (a directed graph's successor
-    // lists) raises status bit 16, which sends the batch through the exact guarded path
+    // lists) raises DADMM_STATUS_RECOMPUTE, which sends the batch through the exact guarded path
     float mf[P][P];
 #pragma unroll
     for (int q = 0; q < P; ++q)
@@ -235,7 +235,7 @@ __device__ __forceinline__ void fused_body(const FusedArgs& a, float* __restrict
                 asym |= e1 != e2;
                 mf[q][p] = e1 ? 1.0f : 0.0f;
             }
-        status |= asym ? 16u : 0u;
+        status |= asym ? DADMM_STATUS_RECOMPUTE : 0;
     }
 
     // per-lane byte offsets into the operator and the output
@@ -292,8 +292,9 @@ __device__ __forceinline__ void fused_body(const FusedArgs& a, float* __restrict
             consensus_ordered<P, 1>(yy, dd, mk, ord);
 #pragma unroll
         for (int p = 0; p < P; ++p) {
-            const float d = mclamp(dd[p][0], -dlim, dlim);
-            const float un = mclamp(U[p][e] + d * et_prev[p], -vclip_prev, vclip_prev);
+            // dual_elem's two atoms (the composite around the select compiles to other code)
+            const float d = delta_clamp<Clamp::MED3>(dd[p][0], dlim);
+            const float un = dual_u<Clamp::MED3>(U[p][e], d, et_prev[p], vclip_prev);
             // k = 0 keeps the caller's U0, delta0 (a select, not a branch: the row stays one
             // basic block, interleavable with the GEMM1 MFMAs)
             D[p][e] = live ? d : D[p][e];
@@ -317,10 +318,7 @@ __device__ __forceinline__ void fused_body(const FusedArgs& a, float* __restrict
         // seq_hyp(k) row(s): (alpha, tau, rho, eta) — kernel-uniform scalars
         float al[P], ta[P], rh[P], et[P];
 #pragma unroll
-        for (int p = 0; p < P; ++p) {
-            const cfloat* hp = (const cfloat*)a.hyp + ((size_t)k * a.hyp_rows + (a.hyp_rows == 1 ? 0 : p)) * 4;
-            al[p] = hp[0]; ta[p] = hp[1]; rh[p] = hp[2]; et[p] = hp[3];
-        }
+        for (int p = 0; p < P; ++p) load_hyp_row(a, k, p, al[p], ta[p], rh[p], et[p]);
         float gclip, vclip;
         iter_clips(a.variant, k, gclip, vclip);
         const bool deferred = k > 0;
@@ -391,23 +389,13 @@ __device__ __forceinline__ void fused_body(const FusedArgs& a, float* __restrict
                 for (int r = 0; r < 4; ++r) {
                     const int e = 4 * tt + r;
                     const float yv = yk[r];
-                    // grad = (AtAy - Atb) + sign(y)*tau + U*deg + delta*rho, left to right;
-                    // sign(y)*tau is exactly +-tau or +0
-                    // (the nested ternary compiles to short divergent branches here; the branch-free
-                    // sign_times() costs 46 spilled VGPRs in this register-bound kernel and measured
-                    // 0.64 vs 0.59 ms at the headline shape)
-                    const float st = sign_times(yv, ta[p]);
-                    float gr = gp[r];
-                    gr = gr + st;
-                    gr = gr + U[p][e] * dg[p];
-                    gr = gr + D[p][e] * rh[p];
+                    // (its sign(y)*tau, exactly +-tau or +0, is branch-free: a nested ternary
+                    // compiles to short divergent branches between the MFMAs)
+                    const float gr = grad_assemble(gp[r], yv, U[p][e], D[p][e], ta[p], dg[p], rh[p]);
                     grv[r] = gr;
                     urv[r] = U[p][e];
                     bad_g |= (gr != gr);                            // :84 guard (flag only)
-                    gr = mclamp(gr, -gclip, gclip);                 // :80-81
-                    float v = yv - al[p] * gr;                      // :89
-                    v = mclamp(v, -vclip, vclip);                   // :92-93
-                    yn[r] = v;
+                    yn[r] = primal_elem<Clamp::MED3>(yv, gr, al[p], gclip, vclip);
                 }
                 *(f32x4*)(Ylds + (p * BT + j) * YS + n0) = yn;
                 // Y[k][s][p][n0..n0+3]; rows past n go to an offset the range check drops
@@ -465,7 +453,7 @@ __device__ __forceinline__ void fused_body(const FusedArgs& a, float* __restrict
             }
 #pragma unroll
             for (int tt = 0; tt < T2; ++tt) primal_update((P - 1) * T2 + tt, gp[(P - 1) & 1][tt]);
-            status |= bad_g ? 4u : 0u;
+            status |= bad_g ? DADMM_STATUS_GRAD_NAN : 0;
         } else if (k + 1 < a.K) {
             for (int t0 = 0; t0 + 1 < RING; ++t0) load_a(aring[t0], t0);
         }

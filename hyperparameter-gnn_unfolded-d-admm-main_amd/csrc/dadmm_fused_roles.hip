@@ -4,7 +4,8 @@
 //
 // Same problem decomposition and the same bits as dadmm_fused.hip (one workgroup = 16 samples x all
 // agents x all K iterations; every dot product the same single fma chain; every element operation
-// as primal_update / the dual update there state it). What differs is who runs what:
+// through the same grad_assemble / primal_elem / dual_elem of dadmm_device.h). What differs is who
+// runs what:
 //   * waves 0-3 (one per SIMD) issue only MFMAs, their operand loads and the accumulator stores:
 //       GEMM1  R_p = A_p y_p - b_p   wave w: m-block w of every agent, agents interleaved;
 //       GEMM2  G_p = A_p^T R_p       wave w: n-tiles 4w..4w+3 of every agent as four interleaved
@@ -326,14 +327,19 @@ __device__ __forceinline__ void roles_update(const FusedArgs& a, float* __restri
     }
     __syncthreads();                     // y_0 in Ylds: the matrix waves start GEMM1(0)
 
-    // the guards of dadmm_fused.hip, bit for bit (status bits 1, 2, 8, 16; 4 in the loop)
-    uint32_t status = (ymag >= 0x7f800000u ? 1u : 0u) | (umag >= 0x7f800000u ? 2u : 0u);
+    // dadmm_fused.hip's guards, restated ("The element update"): the y_0 / U_0
+    // magnitudes, the hyper-parameter table over the update role's 256 threads, the shared graph's
+    // asymmetry (DADMM_STATUS_GRAD_NAN in the loop)
+    uint32_t status = (ymag >= 0x7f800000u ? DADMM_STATUS_Y_NONFINITE : 0) |
+                      (umag >= 0x7f800000u ? DADMM_STATUS_U_NONFINITE : 0);
     {
         bool bad_h = false;
         const int nh = a.K * a.hyp_rows * 4;
         for (int i = threadIdx.x - 256; i < nh; i += 256) bad_h |= !finitef(a.hyp[i]);
-        status |= bad_h ? 8u : 0u;
+        status |= bad_h ? DADMM_STATUS_YNEXT_NAN : 0;
     }
+    // consensus_fma's multiplier table, each multiplier through readfirstlane: provably uniform, so
+    // it is held in an SGPR
     float mf[P][P];
 #pragma unroll
     for (int q = 0; q < P; ++q)
@@ -347,10 +353,9 @@ __device__ __forceinline__ void roles_update(const FusedArgs& a, float* __restri
             for (int p = q + 1; p < P; ++p) {
                 const bool e1 = (msk[q] >> p) & 1u, e2 = (msk[p] >> q) & 1u;
                 asym |= e1 != e2;
-                // (readfirstlane: the multiplier provably uniform, so it is held in an SGPR)
                 mf[q][p] = __uint_as_float(__builtin_amdgcn_readfirstlane(e1 ? 0x3f800000u : 0u));
             }
-        status |= asym ? 16u : 0u;
+        status |= asym ? DADMM_STATUS_RECOMPUTE : 0;
     }
     const uint32_t voffY = (uint32_t)((s * P * n + 4 * h) * 4);           // + (p*n + nb*16)*4
     const float dlim = a.variant != 0 ? GNN_DELTA_LIMIT : __builtin_inff();
@@ -359,10 +364,7 @@ __device__ __forceinline__ void roles_update(const FusedArgs& a, float* __restri
     for (int k = 0; k < a.K; ++k) {
         float al[P], ta[P], rh[P], et[P];
 #pragma unroll
-        for (int p = 0; p < P; ++p) {
-            const cfloat* hp = (const cfloat*)a.hyp + ((size_t)k * a.hyp_rows + (a.hyp_rows == 1 ? 0 : p)) * 4;
-            al[p] = hp[0]; ta[p] = hp[1]; rh[p] = hp[2]; et[p] = hp[3];
-        }
+        for (int p = 0; p < P; ++p) load_hyp_row(a, k, p, al[p], ta[p], rh[p], et[p]);
         float gclip, vclip;
         iter_clips(a.variant, k, gclip, vclip);
         const rsrc_t rY = make_rsrc(a.Y + (size_t)k * B * P * n, state_bytes);
@@ -396,17 +398,9 @@ __device__ __forceinline__ void roles_update(const FusedArgs& a, float* __restri
                 for (int r = 0; r < 4; ++r) {
                     const int e = 4 * tt + r;
                     const float yv = yk[r];
-                    // grad = (AtAy - Atb) + sign(y)*tau + U*deg + delta*rho, left to right
-                    const float st = sign_times(yv, ta[p]);
-                    float gr = gp[r];
-                    gr = gr + st;
-                    gr = gr + U[p][e] * dg[p];
-                    gr = gr + D[p][e] * rh[p];
+                    const float gr = grad_assemble(gp[r], yv, U[p][e], D[p][e], ta[p], dg[p], rh[p]);
                     gmag = max(gmag, __float_as_uint(gr) & 0x7fffffffu);   // :84 guard (flag only)
-                    gr = mclamp(gr, -gclip, gclip);                 // :80-81
-                    float v = yv - al[p] * gr;                      // :89
-                    v = mclamp(v, -vclip, vclip);                   // :92-93
-                    yn[r] = v;
+                    yn[r] = primal_elem<Clamp::MED3>(yv, gr, al[p], gclip, vclip);
                 }
                 gmag = fresh(gmag);      // folded here, not sunk to the loop's end with every row alive
                 *(f32x4*)(Ylds + (p * BT + j) * YS + n0) = yn;
@@ -417,7 +411,7 @@ __device__ __forceinline__ void roles_update(const FusedArgs& a, float* __restri
             }
             __syncthreads();             // stages 1..P
         }
-        status |= gmag > 0x7f800000u ? 4u : 0u;
+        status |= gmag > 0x7f800000u ? DADMM_STATUS_GRAD_NAN : 0;
 
         // delta_{k+1} = 2 L y_{k+1} for the lane's rows (all agents, lane-local), GNN delta clamp,
         // U_{k+1} = clamp(U_k + delta_{k+1} * eta_k) (:95-99). After the last iteration only U_out
@@ -444,11 +438,8 @@ __device__ __forceinline__ void roles_update(const FusedArgs& a, float* __restri
                     }
                     consensus_fma<P>(yy, dd, mf);
 #pragma unroll
-                    for (int p = 0; p < P; ++p) {
-                        const float d = mclamp(dd[p][0], -dlim, dlim);
-                        U[p][e] = mclamp(U[p][e] + d * et[p], -vclip, vclip);
-                        D[p][e] = d;
-                    }
+                    for (int p = 0; p < P; ++p)
+                        dual_elem<Clamp::MED3>(dd[p][0], et[p], dlim, vclip, U[p][e], D[p][e]);
                 }
             }
         }

@@ -591,11 +591,9 @@ __device__ __forceinline__ void update_item(const GnnArgs& a, int k, int item, f
                 if (ok && fix != nullptr) *(f32x4*)(fix + base + (size_t)p * n) = yv[u];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    float g = tv[u][r] - bv[u][r];
-                    g = g + sign_times(yv[u][r], tav[u]);   // sign(y) * tau
-                    g = g + uv[u][r] * dgv[u];
-                    g = g + dv[u][r] * rhv[u];
-                    g = clamp_t(g, -gclip, gclip);
+                    float g = grad_assemble(tv[u][r] - bv[u][r], yv[u][r], uv[u][r], dv[u][r], tav[u], dgv[u],
+                                            rhv[u]);
+                    g = grad_clamp<Clamp::NANPROP>(g, gclip);
                     bad_g |= ok && g != g;                  // after the clamp only NaN (:216)
                     gv[u][r] = ok ? g : 0.0f;
                 }
@@ -617,7 +615,7 @@ __device__ __forceinline__ void update_item(const GnnArgs& a, int k, int item, f
                     const float al = FUSED ? alv[u] : hyp_at(a, s, 0, p);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        v[r] = clamp_t(yv[u][r] - al * gv[u][r], -vclip, vclip);   // :221-225
+                        v[r] = primal_y<Clamp::NANPROP>(yv[u][r], al, gv[u][r], vclip);   // :221-225
                         bad_y |= !finitef(v[r]);
                     }
                     *(f32x4*)(Yk + base + (size_t)p * n) = v;
@@ -664,8 +662,8 @@ __device__ __forceinline__ void update_item(const GnnArgs& a, int k, int item, f
             f32x4 un;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                if (a.variant != 0) acc[r] = clamp_t(acc[r], -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);          // :229
-                un[r] = clamp_t(uv[u][r] + acc[r] * et, -vclip, vclip);              // :231-232
+                if (a.variant != 0) acc[r] = delta_clamp<Clamp::NANPROP>(acc[r], GNN_DELTA_LIMIT);
+                un[r] = dual_u<Clamp::NANPROP>(uv[u][r], acc[r], et, vclip);         // :231-232
                 bad_u |= !finitef(un[r]);
             }
             const size_t off = base + (size_t)p * n;
@@ -719,11 +717,11 @@ __global__ __launch_bounds__(THREADS) void finish_kernel(GnnArgs a) {
             dst[i] = zero ? (f32x4){0.0f, 0.0f, 0.0f, 0.0f} : ((const f32x4*)ys)[i];
     }
     if (blockIdx.x == 0 && threadIdx.x == 0 && a.status != nullptr) {
-        int st = flag_ld(a.flags + GNN_F_Y0) ? 1 : 0;
+        int st = flag_ld(a.flags + GNN_F_Y0) ? DADMM_STATUS_Y_NONFINITE : 0;
         for (int k = 0; k < K; ++k) {
-            st |= flag_ld(a.flags + GNN_F_UBAD(k)) ? 2 : 0;
-            st |= flag_ld(a.flags + GNN_F_GBAD(k)) ? 4 : 0;
-            st |= flag_ld(a.flags + GNN_F_YNB(k)) ? 8 : 0;
+            st |= flag_ld(a.flags + GNN_F_UBAD(k)) ? DADMM_STATUS_U_NONFINITE : 0;
+            st |= flag_ld(a.flags + GNN_F_GBAD(k)) ? DADMM_STATUS_GRAD_NAN : 0;
+            st |= flag_ld(a.flags + GNN_F_YNB(k)) ? DADMM_STATUS_YNEXT_NAN : 0;
         }
         *a.status = st;
     }

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/dadmm.h"   // the DADMM_STATUS_* bits the kernels set
+
 namespace dadmm {
 
 constexpr int BT = 16;       // samples per workgroup of the fused kernel (MFMA N dimension)

@@ -149,7 +149,7 @@ __device__ __forceinline__ void split_body(const SplitArgs& sa, float* __restric
         bool bad_h = false;
         const int nh = a.K * a.hyp_rows * 4;
         for (int i = threadIdx.x; i < nh; i += WV * 64) bad_h |= !finitef(a.hyp[i]);
-        status |= bad_h ? 8u : 0u;
+        status |= bad_h ? DADMM_STATUS_YNEXT_NAN : 0;
     }
     const float dlim = a.variant != 0 ? GNN_DELTA_LIMIT : __builtin_inff();
 
@@ -200,7 +200,7 @@ __device__ __forceinline__ void split_body(const SplitArgs& sa, float* __restric
             }
             // reference guards at the top of an iteration (:55-61) can only fire at k = 0 (see
             // dadmm_fused.hip); the caller's gated recomputation applies them
-            status |= (bad_y ? 1u : 0u) | (bad_u ? 2u : 0u);
+            status |= (bad_y ? DADMM_STATUS_Y_NONFINITE : 0) | (bad_u ? DADMM_STATUS_U_NONFINITE : 0);
         }
         // -b seeds of this wave's GEMM1 chains (slice 0 only; the other slices' chains start at +0)
         f32x4 bseed[THA];
@@ -225,11 +225,7 @@ __device__ __forceinline__ void split_body(const SplitArgs& sa, float* __restric
             const uint32_t slot = (epoch - 1) & 1u;
             float al[THA], ta[THA], rh[THA], et[THA];
 #pragma unroll
-            for (int i = 0; i < TH; ++i) {
-                const int p = HALF + 2 * i;
-                const cfloat* hp = (const cfloat*)a.hyp + ((size_t)k * a.hyp_rows + (a.hyp_rows == 1 ? 0 : p)) * 4;
-                al[i] = hp[0]; ta[i] = hp[1]; rh[i] = hp[2]; et[i] = hp[3];
-            }
+            for (int i = 0; i < TH; ++i) load_hyp_row(a, k, HALF + 2 * i, al[i], ta[i], rh[i], et[i]);
             float gclip, vclip;
             iter_clips(a.variant, k, gclip, vclip);
 
@@ -286,11 +282,8 @@ __device__ __forceinline__ void split_body(const SplitArgs& sa, float* __restric
                 for (int i = 0; i < TH; ++i) {
                     const int p = HALF + 2 * i;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float d = mclamp(dd[p][r], -dlim, dlim);
-                        U[i][r] = mclamp(U[i][r] + d * et_prev[i], -vclip_prev, vclip_prev);
-                        D[i][r] = d;
-                    }
+                    for (int r = 0; r < 4; ++r)
+                        dual_elem<Clamp::MED3>(dd[p][r], et_prev[i], dlim, vclip_prev, U[i][r], D[i][r]);
                 }
             }
 
@@ -348,19 +341,13 @@ __device__ __forceinline__ void split_body(const SplitArgs& sa, float* __restric
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float yv = yk[r];
-                    // grad = (AtAy - Atb) + sign(y)*tau + U*deg + delta*rho, left to right (:73-77)
-                    float gr = gp[r];
-                    gr = gr + sign_times(yv, ta[i]);
-                    gr = gr + U[i][r] * dg[p];
-                    gr = gr + D[i][r] * rh[i];
+                    const float gr = grad_assemble(gp[r], yv, U[i][r], D[i][r], ta[i], dg[p], rh[i]);
                     if constexpr (REC) {
                         grv[r] = gr;
                         urv[r] = U[i][r];
                     }
                     bad_g |= (gr != gr);                            // :84 guard (flag only)
-                    gr = mclamp(gr, -gclip, gclip);                 // :80-81
-                    float v = yv - al[i] * gr;                      // :89
-                    yn[r] = mclamp(v, -vclip, vclip);               // :92-93
+                    yn[r] = primal_elem<Clamp::MED3>(yv, gr, al[i], gclip, vclip);
                 }
                 *(f32x4*)yrow = yn;
                 // Y[k][s][p][n0..n0+3]; rows past n go to an offset the range check drops
@@ -372,7 +359,7 @@ __device__ __forceinline__ void split_body(const SplitArgs& sa, float* __restric
                 }
             }
             __builtin_amdgcn_s_setprio(0);
-            status |= bad_g ? 4u : 0u;
+            status |= bad_g ? DADMM_STATUS_GRAD_NAN : 0;
 #pragma unroll
             for (int i = 0; i < TH; ++i) et_prev[i] = et[i];
             vclip_prev = vclip;
@@ -395,16 +382,15 @@ __device__ __forceinline__ void split_body(const SplitArgs& sa, float* __restric
                 const int p = HALF + 2 * i;
                 f32x4 v;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float d = mclamp(dd[p][r], -dlim, dlim);
-                    v[r] = mclamp(U[i][r] + d * et_prev[i], -vclip_prev, vclip_prev);
-                }
+                for (int r = 0; r < 4; ++r)
+                    v[r] = dual_u<Clamp::MED3>(U[i][r], delta_clamp<Clamp::MED3>(dd[p][r], dlim), et_prev[i],
+                                               vclip_prev);
                 if (rows_ok) bstore4<0>(v, rU, (uint32_t)(((s * P + p) * n + n0) * 4));
             }
         }
         __syncthreads();   // Ylds is rewritten by the next tile's initial state
     }
-    if (aborted) status |= 16u;   // the exact guarded recomputation redoes the batch
+    if (aborted) status |= DADMM_STATUS_RECOMPUTE;   // the exact guarded recomputation redoes the batch
     if (a.status != nullptr) {
         uint32_t wst = status;
 #pragma unroll

@@ -161,12 +161,9 @@ __device__ void phase_grad(const StepArgs& a, int k, int item, float* lds) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float y = yv[r];
-                const float st = sign_times(y, ta);   // sign(y) * tau
-                float g = gc[r] + st;
-                g = g + uv[r] * dg;
-                g = g + dv[r] * rh;
+                float g = grad_assemble(gc[r], y, uv[r], dv[r], ta, dg, rh);
                 gpre[r] = g;
-                g = clamp_t(g, -gclip, gclip);
+                g = grad_clamp<Clamp::NANPROP>(g, gclip);
                 bad |= g != g;                     // after the clamp only NaN remains (:84)
                 gv[r] = g;
             }
@@ -217,7 +214,7 @@ __device__ void phase_update(const StepArgs& a, int k, int item, float* ylds) {
         if (cv) {
             const float g = gzero ? 0.0f : a.G[base + (size_t)p * n];     // :84-86
             const float y = yzero ? 0.0f : ysrc[base + (size_t)p * n];
-            v = clamp_t(y - al * g, -vclip, vclip);                         // :89-93
+            v = primal_y<Clamp::NANPROP>(y, al, g, vclip);
             a.Y[(size_t)k * S + base + (size_t)p * n] = v;
             bad_y |= !finitef(v);
         }
@@ -239,11 +236,11 @@ __device__ void phase_update(const StepArgs& a, int k, int item, float* ylds) {
             const uint8_t* __restrict__ vg = a.vq + v0;
             for (int t = vpl[p]; t < t1; ++t) acc = acc + (yp - yl[(int)vg[t] * 64 + lane]);
         }
-        if (a.variant != 0) acc = clamp_t(acc, -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);             // GNN :229
+        if (a.variant != 0) acc = delta_clamp<Clamp::NANPROP>(acc, GNN_DELTA_LIMIT);
         if (cv) {
             const size_t off = base + (size_t)p * n;
             const float u = uzero ? 0.0f : usrc[off];
-            const float un = clamp_t(u + acc * et, -vclip, vclip);          // :98-99
+            const float un = dual_u<Clamp::NANPROP>(u, acc, et, vclip);
             a.U[off] = un;
             a.D[off] = acc;
             bad_u |= !finitef(un);
@@ -271,13 +268,13 @@ __device__ void phase_final(const StepArgs& a, int wid, int nw) {
             dst[i] = yzero ? (f32x4){0.0f, 0.0f, 0.0f, 0.0f} : ((const f32x4*)ysrc)[i];
     }
     if (wid == 0 && threadIdx.x == 0 && a.status != nullptr) {
-        int st = flag_ld(a.flags + SW_F_Y0) ? 1 : 0;
+        int st = flag_ld(a.flags + SW_F_Y0) ? DADMM_STATUS_Y_NONFINITE : 0;
         for (int k = 0; k < K; ++k) {
-            st |= flag_ld(a.flags + SW_F_UBAD(k)) ? 2 : 0;
-            st |= flag_ld(a.flags + SW_F_GBAD(k)) ? 4 : 0;
-            st |= flag_ld(a.flags + SW_F_YNB(k)) ? 8 : 0;
+            st |= flag_ld(a.flags + SW_F_UBAD(k)) ? DADMM_STATUS_U_NONFINITE : 0;
+            st |= flag_ld(a.flags + SW_F_GBAD(k)) ? DADMM_STATUS_GRAD_NAN : 0;
+            st |= flag_ld(a.flags + SW_F_YNB(k)) ? DADMM_STATUS_YNEXT_NAN : 0;
         }
-        st |= flag_ld(a.flags + SW_F_TIMEOUT) ? 0x100 : 0;
+        st |= flag_ld(a.flags + SW_F_TIMEOUT) ? DADMM_STATUS_BARRIER_TIMEOUT : 0;
         __hip_atomic_store(a.status, st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }

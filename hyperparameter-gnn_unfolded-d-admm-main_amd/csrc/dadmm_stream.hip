@@ -158,7 +158,7 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
             len = a.vptr[g + 1] - v0;
             if (len > DP) {   // cannot come from a graph on P nodes; the exact path takes it
                 len = DP;
-                status |= 16u;
+                status |= DADMM_STATUS_RECOMPUTE;
             }
             for (int t = 0; t < len; ++t) row[t] = (uint32_t)a.vq[v0 + t] * (CT * 64 * 16);
         }
@@ -305,13 +305,13 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
         f32x4 dv = k == 0 ? r.d : acc;
         if (k >= 1 && a.variant != 0) {
 #pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) dv[r4] = tclamp(dv[r4], -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);   // :229
+            for (int r4 = 0; r4 < 4; ++r4) dv[r4] = delta_clamp<Clamp::MINMAX>(dv[r4], GNN_DELTA_LIMIT);
         }
         // the dual update of iteration k - 1 (:98-99), deferred to here (k = 0: U0 as given)
         f32x4 uv;
 #pragma unroll
         for (int r4 = 0; r4 < 4; ++r4) {
-            const float un = tclamp(r.u[r4] + dv[r4] * etp[ai], -vclip_prev, vclip_prev);
+            const float un = dual_u<Clamp::MINMAX>(r.u[r4], dv[r4], etp[ai], vclip_prev);
             uv[r4] = k >= 1 ? un : r.u[r4];
         }
         bad_u0 |= k == 0 && okc && !finite4(uv);
@@ -323,13 +323,10 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
 #pragma unroll
         for (int r4 = 0; r4 < 4; ++r4) {   // :69-93, left to right
             const float y = yo[r4];
-            float gr = gc[r4] + sign_times(y, ta[ai]);
-            gr = gr + uv[r4] * dg[ai];
-            gr = gr + dv[r4] * rh[ai];
+            const float gr = grad_assemble(gc[r4], y, uv[r4], dv[r4], ta[ai], dg[ai], rh[ai]);
             grc[r4] = gr;
             bad_g |= upd && okc && gr != gr;
-            gr = tclamp(gr, -gclip, gclip);
-            const float v = tclamp(y - al[ai] * gr, -vclip, vclip);
+            const float v = primal_elem<Clamp::MINMAX>(y, gr, al[ai], gclip, vclip);
             bad_y |= upd && okc && !finitef(v);
             yn[r4] = okc ? v : 0.0f;
         }
@@ -444,7 +441,8 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
             slot = slot == SLOTS - 1 ? 0 : slot + 1;
         }
     }
-    status |= (bad_y0 ? 1u : 0u) | (bad_u0 ? 2u : 0u) | (bad_g ? 4u : 0u) | ((bad_y || bad_h) ? 8u : 0u);
+    status |= (bad_y0 ? DADMM_STATUS_Y_NONFINITE : 0) | (bad_u0 ? DADMM_STATUS_U_NONFINITE : 0) |
+              (bad_g ? DADMM_STATUS_GRAD_NAN : 0) | ((bad_y || bad_h) ? DADMM_STATUS_YNEXT_NAN : 0);
     if (a.status != nullptr) {
         uint32_t ws = status;
 #pragma unroll

@@ -154,7 +154,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(2))) vo
                     bad |= !(finitef(v[0]) && finitef(v[1]) && finitef(v[2]) && finitef(v[3]));
                 }
             }
-            status |= bad ? 1u : 0u;
+            status |= bad ? DADMM_STATUS_Y_NONFINITE : 0;
         }
         // GEMM1: R = A_p y - b_p, one fma chain per row from -b (wave w = m-blocks w, w + 4, ...
         // of the MB m-groups), one chain per 16-sample half sharing every A load
@@ -261,7 +261,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(2))) vo
     if (!final_only) {
         const float* hk = a.hyp + ((size_t)k * H + hp) * 4;
         al = hk[0]; ta = hk[1]; rh = hk[2]; et = hk[3];
-        status |= (finitef(al) && finitef(ta) && finitef(rh) && finitef(et)) ? 0u : 8u;
+        status |= (finitef(al) && finitef(ta) && finitef(rh) && finitef(et)) ? 0 : DADMM_STATUS_YNEXT_NAN;
         iter_clips(a.variant, k, gclip, vclip);
     }
     if (k > 0) {
@@ -314,11 +314,11 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(2))) vo
             } else {
                 if (a.variant != 0) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) c.dv[g][r] = tclamp(c.dv[g][r], -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);   // :229
+                    for (int r = 0; r < 4; ++r) c.dv[g][r] = delta_clamp<Clamp::MINMAX>(c.dv[g][r], GNN_DELTA_LIMIT);
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    uv[g][r] = tclamp(c.up[g][r] + c.dv[g][r] * et_prev, -vclip_prev, vclip_prev);
+                    uv[g][r] = dual_u<Clamp::MINMAX>(c.up[g][r], c.dv[g][r], et_prev, vclip_prev);
             }
             *(f32x4*)(Ucur + off[g]) = uv[g];          // U_k (the ping-pong buffer / U_out)
         }
@@ -341,13 +341,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(2))) vo
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float y = c.yp[g][r];
-                    const float st = sign_times(y, ta);   // sign(y) * tau
-                    float gr = gc[r] + st;
-                    gr = gr + uv[g][r] * dg[hh];
-                    gr = gr + c.dv[g][r] * rh;
+                    const float gr = grad_assemble(gc[r], y, uv[g][r], c.dv[g][r], ta, dg[hh], rh);
                     bad_g |= gr != gr;
-                    gr = tclamp(gr, -gclip, gclip);
-                    const float v = tclamp(y - al * gr, -vclip, vclip);
+                    const float v = primal_elem<Clamp::MINMAX>(y, gr, al, gclip, vclip);
                     bad_y |= !finitef(v);
                     yn[r] = v;
                 }
@@ -371,7 +367,8 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(2))) vo
             compute_chunk(c0, cA);
         }
     }
-    status |= (bad_u0 ? 2u : 0u) | (bad_g ? 4u : 0u) | (bad_y ? 8u : 0u);
+    status |= (bad_u0 ? DADMM_STATUS_U_NONFINITE : 0) | (bad_g ? DADMM_STATUS_GRAD_NAN : 0) |
+              (bad_y ? DADMM_STATUS_YNEXT_NAN : 0);
     if (a.status != nullptr) {
         uint32_t ws = status;
 #pragma unroll
@@ -554,7 +551,7 @@ __global__ __launch_bounds__(THREADS) void colupdate_kernel(TiledArgs a, int k, 
             const float* hk = a.hyp + ((size_t)k * H + hp) * 4;
             al = hk[0]; ta = hk[1]; rh = hk[2];
             const float et = hk[3];
-            status |= (finitef(al) && finitef(ta) && finitef(rh) && finitef(et)) ? 0u : 8u;
+            status |= (finitef(al) && finitef(ta) && finitef(rh) && finitef(et)) ? 0 : DADMM_STATUS_YNEXT_NAN;
         }
         if (k > 0) et_prev = a.hyp[((size_t)(k - 1) * H + hp) * 4 + 3];
         // every global operand of this agent is issued first (R_p, A_p^T rows, U_{k-1}, d0); the
@@ -627,7 +624,7 @@ __global__ __launch_bounds__(THREADS) void colupdate_kernel(TiledArgs a, int k, 
                     for (int hh = 0; hh < HALVES; ++hh)
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
-                            dv[nt][hh][r] = tclamp(dv[nt][hh][r], -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);   // :229
+                            dv[nt][hh][r] = delta_clamp<Clamp::MINMAX>(dv[nt][hh][r], GNN_DELTA_LIMIT);
             }
         }
 #pragma unroll
@@ -643,7 +640,7 @@ __global__ __launch_bounds__(THREADS) void colupdate_kernel(TiledArgs a, int k, 
                 } else {
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        uv[r] = tclamp(up[nt][hh][r] + dv[nt][hh][r] * et_prev, -vclip_prev, vclip_prev);
+                        uv[r] = dual_u<Clamp::MINMAX>(up[nt][hh][r], dv[nt][hh][r], et_prev, vclip_prev);
                 }
                 if (ok) *(f32x4*)(Ucur + off[nt][hh]) = uv;           // U_k
                 if (final_only) continue;
@@ -657,13 +654,9 @@ __global__ __launch_bounds__(THREADS) void colupdate_kernel(TiledArgs a, int k, 
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const float y = yv[nt][hh][r];
-                        const float st = sign_times(y, ta);
-                        float gr = gc[r] + st;
-                        gr = gr + uv[r] * dg[hh];
-                        gr = gr + dv[nt][hh][r] * rh;
+                        const float gr = grad_assemble(gc[r], y, uv[r], dv[nt][hh][r], ta, dg[hh], rh);
                         bad_g |= gr != gr;
-                        gr = tclamp(gr, -gclip, gclip);
-                        const float v = tclamp(y - al * gr, -vclip, vclip);
+                        const float v = primal_elem<Clamp::MINMAX>(y, gr, al, gclip, vclip);
                         bad_y |= !finitef(v);
                         yn[r] = v;
                     }
@@ -672,7 +665,8 @@ __global__ __launch_bounds__(THREADS) void colupdate_kernel(TiledArgs a, int k, 
             }
         }
     }
-    status |= (bad_u0 ? 2u : 0u) | (bad_g ? 4u : 0u) | (bad_y ? 8u : 0u);
+    status |= (bad_u0 ? DADMM_STATUS_U_NONFINITE : 0) | (bad_g ? DADMM_STATUS_GRAD_NAN : 0) |
+              (bad_y ? DADMM_STATUS_YNEXT_NAN : 0);
     if (a.status != nullptr) {
         uint32_t ws = status;
 #pragma unroll
