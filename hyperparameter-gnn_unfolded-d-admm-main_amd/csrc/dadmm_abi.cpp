@@ -685,6 +685,39 @@ size_t dadmm_tiled_scratch_bytes(const dadmm_dims* d) {
            align256(sizeof(float) * (size_t)d->B * d->P * m_pad_of(d));
 }
 
+// The shape conditions of dadmm_forward_tiled(_record), shared with the dadmm_tiled_form query.
+static int tiled_shape_check(const dadmm_dims* d) {
+    int rc;
+    if (m_pad_of(d) > 2 * dadmm::M_PAD)   // iter_kernel<MB>, stream_kernel<., ., ., MB>: MB in {1, 2}
+        return fail(DADMM_EUNSUPPORTED, "m=%d > %d rows per agent: not a tiled shape", d->m,
+                    2 * dadmm::M_PAD);
+    if ((rc = check_n4(d)) != DADMM_OK || (rc = check_iterate(d)) != DADMM_OK) return rc;
+    if (dadmm::tiled_lds_bytes(n_pad_of(d), m_pad_of(d)) > 160 * 1024)
+        return fail(DADMM_EUNSUPPORTED, "n=%d: the y tile does not fit the LDS", d->n);
+    return DADMM_OK;
+}
+// Recording runs on the streamed single-launch form only.
+static int tiled_record_check(const dadmm_dims* d, const dadmm::TiledArgs& a) {
+    if ((size_t)d->K * d->B * d->P * d->n * 4 >= ((size_t)1 << 40))
+        return fail(DADMM_EINVAL, "recording too large");
+    if (dadmm::tiled_form(a, true) != 1)
+        return fail(DADMM_EUNSUPPORTED, "recording on the tiled path needs the streamed form (P <= 16 at "
+                                        "m <= 64, P <= 8 at m <= 128; n_pad >= 128): use dadmm_forward_stepwise");
+    return DADMM_OK;
+}
+
+int dadmm_tiled_form(const dadmm_dims* d, int32_t record) {
+    int rc = check_dims(d);
+    if (rc) return rc;
+    if (d->B == 0 || d->K == 0) return ok();   // nothing is launched
+    if ((rc = tiled_shape_check(d)) != DADMM_OK) return rc;
+    dadmm::TiledArgs a{};
+    fill_args_padded(a, d, nullptr);
+    if (record != 0 && (rc = tiled_record_check(d, a)) != DADMM_OK) return rc;
+    ok();
+    return dadmm::tiled_form(a, record != 0);
+}
+
 static int forward_tiled_impl(const dadmm_dims* d, const void* op, const float* b,
                               const int32_t* visit_ptr, const uint8_t* visit_q, const float* deg,
                               const float* hyp, const float* y0, const float* U0, const float* d0,
@@ -698,12 +731,7 @@ static int forward_tiled_impl(const dadmm_dims* d, const void* op, const float* 
     if (!all_aligned16(op, Y, y0, U0, d0, U_out))
         return fail(DADMM_EINVAL, "op, Y, y0, U0, d0 and U_out must be 16-byte aligned");
     if ((rc = check_scratch256(scratch)) != DADMM_OK) return rc;
-    if (m_pad_of(d) > 2 * dadmm::M_PAD)   // iter_kernel<MB>: MB in {1, 2}
-        return fail(DADMM_EUNSUPPORTED, "m=%d > %d rows per agent: not a tiled shape", d->m,
-                    2 * dadmm::M_PAD);
-    if ((rc = check_n4(d)) != DADMM_OK || (rc = check_iterate(d)) != DADMM_OK) return rc;
-    if (dadmm::tiled_lds_bytes(n_pad_of(d), m_pad_of(d)) > 160 * 1024)
-        return fail(DADMM_EUNSUPPORTED, "n=%d: the y tile does not fit the LDS", d->n);
+    if ((rc = tiled_shape_check(d)) != DADMM_OK) return rc;
     const size_t state = align256(sizeof(float) * (size_t)d->B * d->P * d->n);
     dadmm::TiledArgs a{};
     fill_args_padded(a, d, op);
@@ -725,13 +753,9 @@ static int forward_tiled_impl(const dadmm_dims* d, const void* op, const float* 
     if (Grec != nullptr || Urec != nullptr) {   // recording: the streamed single-launch form only
         if (any_null(Grec, Urec) || !all_aligned16(Grec, Urec))
             return fail(DADMM_EINVAL, "Grec and Urec: both, 16-byte aligned");
-        if ((size_t)d->K * d->B * d->P * d->n * 4 >= ((size_t)1 << 40))
-            return fail(DADMM_EINVAL, "recording too large");
+        if ((rc = tiled_record_check(d, a)) != DADMM_OK) return rc;
         a.Grec = Grec;
         a.Urec = Urec;
-        if (!dadmm::stream_applies(a))
-            return fail(DADMM_EUNSUPPORTED, "recording on the tiled path needs the streamed form (P <= 16, "
-                                            "m <= 64, n_pad >= 128): use dadmm_forward_stepwise");
         return hip_rc(dadmm::launch_stream(a, (hipStream_t)stream), "streamed recording launch");
     }
     return hip_rc(dadmm::launch_tiled(a, (hipStream_t)stream), "tiled launch");

@@ -196,6 +196,9 @@ hipError_t launch_tiled(const TiledArgs& a, hipStream_t stream);
 // the whole forward in one launch, state streamed once per iteration (dadmm_stream.hip); U_k in
 // place in a.Ubuf[0]
 bool stream_applies(const TiledArgs& a);
+// 1: the streamed launch serves `a` (recording or not) in the current environment, 0: the
+// per-iteration launches do (there is no recording form of those)
+int tiled_form(const TiledArgs& a, bool record);
 hipError_t launch_stream(const TiledArgs& a, hipStream_t stream);
 
 // ---- fused loss (dadmm_loss.hip) ----------------------------------------------------------------

@@ -1,6 +1,7 @@
 // dadmm_stream.hip — the whole K-iteration forward in ONE launch for the shapes whose per-sample
 // state does not fit on chip (BASELINE configs[2]: P = 16, n = 512, m = 64): the state streams
-// through HBM exactly once per iteration, R_k stays in registers between iterations.
+// through HBM exactly once per iteration, R_k stays in registers between iterations. With two
+// 64-row groups per agent (MB = 2, P <= 8) it also holds the reference's default shape m = 100.
 //
 // Reference semantics: unfolded_DLASSO.py:53-107 / :127-140 (and the GNN variant's clamps,
 // gnn_dlasso_models_progressive.py:205-232), in the order of oracle_forward_f32.
@@ -107,8 +108,14 @@ size_t lds_bytes(int NWT, int PW, int P) {
 // A wave's work in a step is PW x CT tiles (agent, 16 columns); the global operands of a tile (its
 // A^T and A rows, U_{k-1}, d0) are fetched into a two-deep register ring during the previous tile
 // (across steps and phases), so they land under that tile's MFMAs and the next consensus walk.
+//
+// MB = 64-row groups per agent (m_pad = 64 MB). With two groups a tile's A^T and A rows are 2 x 32
+// VGPRs, so the ring's unit is a (tile, group) half: the next tile's half g is issued right behind
+// the MFMAs that read this tile's half g (A^T behind GEMM2's, A behind GEMM1's), into the registers
+// they free. Every load still has about a tile to land; only U and d0 are held twice.
+template <int MB>
 struct Ring {
-    f32x4 at[4], am[4], u, d;
+    f32x4 at[4 * MB], am[4 * MB], u, d;
 };
 
 // At the top of step bs the DMA of step bs (issued at the top of step bs - 2) and every store of
@@ -122,9 +129,13 @@ __device__ __forceinline__ void wait_prev_step(int kprev, int K) {
     else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
 }
 
-template <int NWT, int PW, bool REC = false>
+template <int NWT, int PW, bool REC = false, int MB = 1>
 __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
+    static_assert(MB == 1 || (MB == 2 && NWT == 8 && PW == 1), "two m-groups: one agent per wave, 8 waves");
     constexpr int NW = NWT;
+    constexpr int MT = 4 * MB;        // 16-row blocks per agent
+    constexpr int MP = 64 * MB;       // padded rows per agent (a.m_pad)
+    using Ring = stream::Ring<MB>;
     constexpr bool RING = NWT == 8;   // the operand ring one tile ahead (two waves per SIMD)
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int PA = NW * PW;
@@ -199,7 +210,7 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
     // is merged from two different loads across a branch (each such merge costs a full vmcnt wait).
     // (descriptors are built per use from a selected base and size: selecting between descriptor
     // values puts them on the stack)
-    const uint32_t at_bytes = (uint32_t)((size_t)P * NP * 64 * 4);
+    const uint32_t at_bytes = (uint32_t)((size_t)P * NP * MP * 4);
     // launch-constant descriptors; a phase or lane without the operand gets an out-of-range offset
     // (zeros, no memory access) instead of a different descriptor
     const rsrc_t dA = make_rsrc(a.A, at_bytes);
@@ -208,6 +219,33 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
     // the global operands of tile i = (agent i / CT, columns 16 (i % CT)) of step bs: fetch_a (A^T
     // rows, U_{k-1}, d0) is issued at the start of the previous tile, fetch_m (A rows, needed only at
     // the tile's end) after the previous tile's GEMM2, when its A^T registers are free
+    // (two m-groups: in halves g of 64 rows, each re-issued as soon as its registers are free)
+    auto fetch_at = [&](int k, int c0, int i, Ring& r, int g) {
+        const int ai = i / CT, ct = i % CT;
+        const int p = w + NW * ai;
+        const bool pin = p < P;
+        const int pc = pin ? p : 0;
+        // lane (j, bq), m-block t: A_p rows 16 t + 4 bq + r, column c0 + 16 ct + j
+        const uint32_t voa = (k >= 0 && k < K && pin) ? (uint32_t)(((4 * bq) * NP + j) * 4) : 0x80000000u;
+        const uint32_t sba = (uint32_t)((((size_t)pc * MP) * NP + c0 + 16 * ct) * 4);
+#pragma unroll
+        for (int t = 4 * g; t < 4 * g + 4; ++t)
+#pragma unroll
+            for (int r4 = 0; r4 < 4; ++r4)
+                r.at[t][r4] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
+                    dA, voa, sba + (uint32_t)((16 * t + r4) * NP * 4), 0));   // row step in soffset
+    };
+    auto fetch_ud = [&](int k, int c0, int i, Ring& r) {
+        const int ai = i / CT, ct = i % CT;
+        const int p = w + NW * ai;
+        const bool pin = p < P;
+        const int pc = pin ? p : 0;
+        const uint32_t off = (pin && col_ok(c0, ct)) ? (uint32_t)(elem(pc, c0, ct) * 4) : 0x80000000u;
+        // U_{k-1} (k = 0: U0 itself; k = 1: U_0 = U0)
+        r.u = bload4(make_rsrc(k <= 1 ? a.U0 : a.Ubuf[0], s_bytes), k >= 0 ? off : 0x80000000u);
+        r.d = bload4(dd0, k == 0 ? off : 0x80000000u);
+    };
+    // (one m-group: the whole tile at once)
     auto fetch_a = [&](int k, int c0, int i, Ring& r) {
         const int ai = i / CT, ct = i % CT;
         const int p = w + NW * ai;
@@ -227,6 +265,17 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
         r.u = bload4(make_rsrc(k <= 1 ? a.U0 : a.Ubuf[0], s_bytes), k >= 0 ? off : 0x80000000u);
         r.d = bload4(dd0, k == 0 ? off : 0x80000000u);
     };
+    auto fetch_am = [&](int k, int c0, int i, Ring& r, int g) {
+        const int ai = i / CT, ct = i % CT;
+        const int p = w + NW * ai;
+        const bool pin = p < P;
+        const int pc = pin ? p : 0;
+        const bool ok = k < K - 1 && pin;
+#pragma unroll
+        for (int t = 4 * g; t < 4 * g + 4; ++t)
+            r.am[t] = bload4(dA, ok ? vam + (uint32_t)(16 * t * NP * 4) : 0x80000000u,
+                             (uint32_t)((((size_t)pc * MP) * NP + c0 + 16 * ct) * 4));
+    };
     auto fetch_m = [&](int k, int c0, int i, Ring& r) {
         const int ai = i / CT, ct = i % CT;
         const int p = w + NW * ai;
@@ -239,22 +288,25 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
                              (uint32_t)((((size_t)pc * 64) * NP + c0 + 16 * ct) * 4));
     };
 
-    f32x4 Rk[PW][4], Rn[PW][4];
+    f32x4 Rk[PW][MT], Rn[PW][MT];
 #pragma unroll
     for (int ai = 0; ai < PW; ++ai)
 #pragma unroll
-        for (int t = 0; t < 4; ++t) Rk[ai][t] = Rn[ai][t] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+        for (int t = 0; t < MT; ++t) Rk[ai][t] = Rn[ai][t] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
     bool bad_y0 = false, bad_u0 = false, bad_g = false, bad_y = false, bad_h = false;
     float al[PW], ta[PW], rh[PW], etp[PW];
     float gclip = 0.0f, vclip = 0.0f, vclip_prev = 0.0f;
 
     // tile i of step bs (phase k, columns c0), operands in r; pre() issues the next tile's A^T rows,
-    // U and d0 after the consensus walk, mid() its A rows after GEMM2.
+    // U and d0 after the consensus walk, mid() its A rows after GEMM2. With two m-groups the next
+    // tile's A^T half g is issued by pre_at(g) behind GEMM2's half g, U and d0 by pre() behind the
+    // last of them, and its A half g by mid_am(g) behind GEMM1's half g (mid() is then empty).
     // Straight-line in every phase: no global load or store sits under a branch (a zero-size descriptor
     // or an out-of-range offset disables one), because the compiler's wait analysis turns a memory
     // operation on one path of a merge into a full vmcnt wait after it. GEMM2 and the update run
     // in the phases without a primal update too (on A^T = 0; nothing is stored).
-    auto compute = [&](int k, int c0, const float* ys, int i, Ring& r, auto&& pre, auto&& mid) {
+    auto compute = [&](int k, int c0, const float* ys, int i, Ring& r, auto&& pre, auto&& mid,
+                       auto&& pre_at, auto&& mid_am) {
         const int ai = i / CT, ct = i % CT;
         const int p = w + NW * ai;
         const bool okc = p < P && col_ok(c0, ct);   // agents p >= P: work on zeros, nothing stored
@@ -284,17 +336,22 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
             }
             return acc;
         };
-        // GEMM2: A_p^T R_k, this tile's columns (16 dependent MFMAs, no input from the walk).
+        // GEMM2: A_p^T R_k, this tile's columns (16 MB dependent MFMAs, one chain over the row
+        // blocks in ascending order across the m-groups; no input from the walk).
         // (The two waves of a SIMD taking the walk and GEMM2 in opposite orders measured 6.18-6.31
         // vs 6.13-6.19 ms.)
         auto gemm2 = [&]() {
-            __builtin_amdgcn_s_setprio(1);
             f32x4 g = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-            for (int t = 0; t < 4; ++t)
+            for (int h = 0; h < MB; ++h) {
+                __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-                for (int r4 = 0; r4 < 4; ++r4) g = mfma4(r.at[t][r4], Rk[ai][t][r4], g);
-            __builtin_amdgcn_s_setprio(0);
+                for (int t = 4 * h; t < 4 * h + 4; ++t)
+#pragma unroll
+                    for (int r4 = 0; r4 < 4; ++r4) g = mfma4(r.at[t][r4], Rk[ai][t][r4], g);
+                __builtin_amdgcn_s_setprio(0);
+                if constexpr (MB > 1) pre_at(h);
+            }
             return g;
         };
         const f32x4 acc = walk();
@@ -339,22 +396,33 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
         bad_y0 |= k == -1 && okc && !finite4(yo);   // the :55 guard on y_0
         // GEMM1: R_{k+1} += A_p[:, tile] y_{k+1}[tile] (phase -1: R_0 from y_0)
         const f32x4 gin = k == -1 ? yo : yn;
-        if (k < K - 1) {
-            __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-            for (int t = 0; t < 4; ++t)
+        for (int h = 0; h < MB; ++h) {
+            if (k < K - 1) {
+                __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-                for (int r4 = 0; r4 < 4; ++r4) Rn[ai][t] = mfma4(r.am[t][r4], gin[r4], Rn[ai][t]);
-            __builtin_amdgcn_s_setprio(0);
+                for (int t = 4 * h; t < 4 * h + 4; ++t)
+#pragma unroll
+                    for (int r4 = 0; r4 < 4; ++r4) Rn[ai][t] = mfma4(r.am[t][r4], gin[r4], Rn[ai][t]);
+                __builtin_amdgcn_s_setprio(0);
+            }
+            if constexpr (MB > 1) mid_am(h);   // (outside the branch, like every load)
         }
     };
 
     Ring r0, r1;
     dma(-1, 0, lds);          // (NB >= 4: stream_applies)
     dma(-1, 1, lds + SF);
-    if constexpr (RING) {
+    if constexpr (RING && MB == 1) {
         fetch_a(-1, 0, 0, r0);
         fetch_m(-1, 0, 0, r0);
+    }
+    if constexpr (MB == 2) {
+        fetch_at(-1, 0, 0, r0, 0);
+        fetch_at(-1, 0, 0, r0, 1);
+        fetch_ud(-1, 0, 0, r0);
+        fetch_am(-1, 0, 0, r0, 0);
+        fetch_am(-1, 0, 0, r0, 1);
     }
     int bs = 0;
     int slot = 0;                                        // bs % SLOTS
@@ -379,7 +447,7 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
 #pragma unroll
             for (int ai = 0; ai < PW; ++ai)
 #pragma unroll
-                for (int t = 0; t < 4; ++t) Rk[ai][t] = Rn[ai][t];
+                for (int t = 0; t < MT; ++t) Rk[ai][t] = Rn[ai][t];
         }
         {   // (unconditional: Rn is dead in phases K - 1 and K)
             const bool bk = k < K - 1;
@@ -387,7 +455,7 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
             for (int ai = 0; ai < PW; ++ai) {
                 const int p = w + NW * ai;
 #pragma unroll
-                for (int t = 0; t < 4; ++t)
+                for (int t = 0; t < MT; ++t)
 #pragma unroll
                     for (int r4 = 0; r4 < 4; ++r4) {
                         const int row = 16 * t + 4 * bq + r4;
@@ -420,7 +488,7 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
                 constexpr int i = decltype(ic)::value;
                 if constexpr (!RING) {   // four waves per SIMD: A^T / U / d0 loaded at the tile's start,
                     fetch_a(k, c0, i, r0);   // A after GEMM2 (into the A^T registers' room)
-                    compute(k, c0, ys, i, r0, [] {}, [&] { fetch_m(k, c0, i, r0); });
+                    compute(k, c0, ys, i, r0, [] {}, [&] { fetch_m(k, c0, i, r0); }, [](int) {}, [](int) {});
                     return;
                 }
                 Ring& cur = (i & 1) ? r1 : r0;
@@ -429,8 +497,13 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
                 const int tk = last ? nk : k, tc0 = last ? nc0 : c0;
                 constexpr int ni = last ? 0 : i + 1;
                 // (past the last step the fetch reads harmless valid memory or nothing)
-                compute(k, c0, ys, i, cur, [&] { fetch_a(tk, tc0, ni, nxt); },
-                        [&] { fetch_m(tk, tc0, ni, nxt); });
+                if constexpr (MB == 1)
+                    compute(k, c0, ys, i, cur, [&] { fetch_a(tk, tc0, ni, nxt); },
+                            [&] { fetch_m(tk, tc0, ni, nxt); }, [](int) {}, [](int) {});
+                else
+                    compute(k, c0, ys, i, cur, [&] { fetch_ud(tk, tc0, ni, nxt); }, [] {},
+                            [&](int g) { fetch_at(tk, tc0, ni, nxt, g); },
+                            [&](int g) { fetch_am(tk, tc0, ni, nxt, g); });
             };
             tile(std::integral_constant<int, 0>{});
             tile(std::integral_constant<int, 1>{});
@@ -453,10 +526,12 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
 
 }  // namespace stream
 
-// The streamed single-launch form applies to m <= 64 rows per agent, P <= 16 agents, and at least
+// The streamed single-launch form applies to P <= 16 agents with m <= 64 rows each, or P <= 8 agents
+// with 64 < m <= 128 (two m-groups, one agent per wave: stream_kernel<8, 1, ., 2>), and at least
 // four 32-column blocks (the ring reads Y[k - 1]'s block >= 2 steps after it was written).
 // waves per workgroup: DADMM_STREAM_WAVES=16 runs one agent per wave (P <= 16, 128 VGPRs, four
-// waves per SIMD) instead of the default 8 waves with two agents each
+// waves per SIMD) instead of the default 8 waves with two agents each; it has no two-group build,
+// so under it m > 64 stays on the per-iteration launches
 static int stream_waves(int P) {
     const char* e = getenv("DADMM_STREAM_WAVES");
     return (e != nullptr && atoi(e) == 16 && P <= 16) ? 16 : stream::NW;
@@ -464,11 +539,40 @@ static int stream_waves(int P) {
 
 bool stream_applies(const TiledArgs& a) {
     const int nw = stream_waves(a.P);
-    return a.m_pad == 64 && a.P >= 1 && a.P <= 2 * stream::NW && a.n_pad % stream::CW == 0 &&
+    const bool rows = a.m_pad == 64 || (a.m_pad == 128 && a.P <= stream::NW && nw == stream::NW);
+    return rows && a.P >= 1 && a.P <= 2 * stream::NW && a.n_pad % stream::CW == 0 &&
            a.n_pad / stream::CW >= 4 && stream::lds_bytes(nw, (a.P + nw - 1) / nw, a.P) <= 160 * 1024;
 }
 
+// Whether the unset DADMM_TILED_STREAM takes the streamed form at m_pad == 128 (inference; DESIGN.md
+// §4.7b has the measurement that decides it). m_pad == 64 always does.
+constexpr bool STREAM_M128_DEFAULT = false;
+
+// The form dadmm_forward_tiled (record = false) / dadmm_forward_tiled_record (record = true) runs for
+// `a`: 1 = the streamed single launch, 0 = the per-iteration launches (recording has none: the
+// caller reports it as unsupported). launch_tiled and the dadmm_tiled_form query both ask here.
+int tiled_form(const TiledArgs& a, bool record) {
+    if (!stream_applies(a)) return 0;
+    if (record) return 1;
+    const char* senv = getenv("DADMM_TILED_STREAM");
+    if (senv != nullptr) return atoi(senv) != 0 ? 1 : 0;
+    return (a.m_pad == 64 || STREAM_M128_DEFAULT) ? 1 : 0;
+}
+
 hipError_t launch_stream(const TiledArgs& a, hipStream_t st) {
+    const int grid = (a.B + BT - 1) / BT;
+    if (a.m_pad == 128) {   // two m-groups: P <= 8, 8 waves (stream_applies)
+        const bool rec = a.Grec != nullptr;
+        const void* kern = rec ? (const void*)stream::stream_kernel<8, 1, true, 2> : (const void*)stream::stream_kernel<8, 1, false, 2>;
+        const size_t lds = stream::lds_bytes(8, 1, a.P);
+        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        if (rec)
+            hipLaunchKernelGGL((stream::stream_kernel<8, 1, true, 2>), dim3(grid), dim3(64 * 8), lds, st, a);
+        else
+            hipLaunchKernelGGL((stream::stream_kernel<8, 1, false, 2>), dim3(grid), dim3(64 * 8), lds, st, a);
+        return hipGetLastError();
+    }
     const int nw = stream_waves(a.P);
     const int PW = (a.P + nw - 1) / nw;
     const void* kern = nw == 16 ? (const void*)stream::stream_kernel<16, 1>
@@ -476,7 +580,6 @@ hipError_t launch_stream(const TiledArgs& a, hipStream_t st) {
     const size_t lds = stream::lds_bytes(nw, PW, a.P);
     hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    const int grid = (a.B + BT - 1) / BT;
     if (a.Grec != nullptr) {   // recording (8 waves)
         const void* rk = PW == 1 ? (const void*)stream::stream_kernel<8, 1, true> : (const void*)stream::stream_kernel<8, 2, true>;
         const size_t rl = stream::lds_bytes(8, (a.P + 7) / 8, a.P);

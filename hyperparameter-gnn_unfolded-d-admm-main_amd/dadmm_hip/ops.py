@@ -114,6 +114,15 @@ class ForwardPlan:
     nzero: int              # int32 words the prologue zeroes: status + pad, epochs, guard flags
 
 
+# The streamed recording launch with two m-groups (64 < m <= 128, P <= 8) runs one workgroup per
+# 16 samples, one wave per agent, and its time barely depends on the batch (2.9 ms at B = 32,
+# 3.5 ms at B = 4096 for P = 5, m = 100, n = 500, K = 25), while the stepwise recording spreads a
+# small batch over (tile, agent) workgroups (1.0 ms at B = 32, 5.2 ms at B = 4096). On "auto" a
+# recording forward at m > 64 therefore takes the streamed launch only from this batch size on
+# (DESIGN.md §4.7b has the sweep); path="tiled" takes it at every batch size.
+STREAM_RECORD_M128_MIN_B = 4096
+
+
 def plan_forward(d: _lib.Dims, fused_ok: bool, *, path: str = "auto", record: bool = False,
                  train_split: bool = False) -> ForwardPlan:
     """The dispatch table of forward_raw's docstring as data. No tensors, no allocation, no
@@ -135,6 +144,8 @@ def plan_forward(d: _lib.Dims, fused_ok: bool, *, path: str = "auto", record: bo
     table = {"auto": ("fused", tiled) if fused_ok else (tiled,), "fused": ("fused",),
              "tiled": (tiled,), "stepwise": ()}
     candidates = ("split",) if split_b else table[path]
+    if path == "auto" and record and d.m > 64 and d.B < STREAM_RECORD_M128_MIN_B:
+        candidates = tuple(c for c in candidates if c != "tiled_record")   # the stepwise launch records
     gated = path in ("auto", "stepwise")
     flag_b = L.dadmm_split_flag_bytes(dp) if split_b else 0
     return ForwardPlan(candidates, gated, split_b, flag_b,
@@ -184,6 +195,7 @@ def forward_raw(op: PreparedOperator, b: torch.Tensor, graphs: GraphBatch, hyp: 
       auto      fused_ok, split serves, not record or train_split split                  yes
       auto      fused_ok, otherwise                               fused, tiled[_record]  yes
       auto      not fused_ok                                      tiled[_record]         yes
+      auto      record, m > 64, B < STREAM_RECORD_M128_MIN_B      the above less tiled_record
       fused     fused_ok, else ValueError                         fused                  no
       split     fused_ok and split serves, else ValueError        split                  no
       tiled                                                       tiled[_record]         no
@@ -194,7 +206,8 @@ def forward_raw(op: PreparedOperator, b: torch.Tensor, graphs: GraphBatch, hyp: 
     order (``split_cols``), which differs from the fused order in fp32 rounding.
 
     record: also store the trajectory the adjoint consumes (the *_record entry of each launcher;
-    tiled_record is the streamed single launch, P <= 16, m <= 64; the stepwise kernels record
+    tiled_record is the streamed single launch, P <= 16 at m <= 64 or P <= 8 at m <= 128 —
+    ``tiled_form(d, record=True) == 1`` —, and unsupported elsewhere; the stepwise kernels record
     when they run). It keeps the fused order at every batch size unless train_split (ignored
     without record) or path "split" opts into the split order; the adjoints consume either.
 
@@ -273,6 +286,21 @@ def split_cols(op: PreparedOperator, B: int, K: int, graphs: GraphBatch = None, 
     d = op.dims(B=B, K=K, hyp_rows=hyp_rows, graph_shared=shared)
     with torch.cuda.device(op.device):
         return _split_cols(d, graphs is None or graphs.fused_ok, record, train_split)
+
+
+def tiled_form(dims_or_shape, record: bool = False) -> int:
+    """Which form the tiled launcher runs (dadmm_tiled_form; no GPU needed): 1 the streamed single
+    launch, 0 the per-iteration launches, or the negative DADMM_E* code the entry point would
+    return for the shape (``record``: dadmm_forward_tiled_record, which has the streamed form
+    only). It reads DADMM_TILED_STREAM / DADMM_STREAM_WAVES as the launch does. dims_or_shape: a
+    ``_lib.Dims``, or (P, m, n) for a batch of 16, K = 1, one hyper-parameter row, a shared graph
+    (none of which the choice depends on)."""
+    d = dims_or_shape
+    if not isinstance(d, _lib.Dims):
+        P, m, n = d
+        d = _lib.Dims(B=16, P=P, m=m, n=n, K=1, variant=_lib.VARIANT_UNFOLDED, hyp_rows=1,
+                      graph_shared=1)
+    return int(_lib.load().dadmm_tiled_form(ctypes.byref(d), 1 if record else 0))
 
 
 class Trajectory:

@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define DADMM_ABI_VERSION 19
+#define DADMM_ABI_VERSION 20
 
 enum {
     DADMM_OK = 0,
@@ -216,7 +216,11 @@ size_t dadmm_tiled_scratch_bytes(const dadmm_dims* d);
  * n = 512), state in HBM. For P <= 16, m <= 64, n_pad >= 128 it is ONE launch (the streamed form,
  * dadmm_stream.hip: 16 samples x all agents per workgroup, y_k staged per 32-column block, R_k in
  * registers, the next iteration's GEMM1 fused into the update; environment DADMM_TILED_STREAM=0
- * selects the per-iteration launches below instead). Otherwise two launches per iteration: a consensus launch forms
+ * selects the per-iteration launches below instead). The streamed form also serves 64 < m <= 128
+ * at P <= 8 (the reference's default shape m = 100, n = 500), but there only when
+ * DADMM_TILED_STREAM=1 asks for it: unset, such a shape takes the per-iteration launches, which
+ * measured faster at small batches (one streamed workgroup holds 16 samples of every agent).
+ * dadmm_tiled_form tells which form a call runs. Otherwise two launches per iteration: a consensus launch forms
  * delta_k for every agent of a sample from y_k (visit lists, the reference's order; scratch), then
  * each (32-sample tile, agent) workgroup applies the deferred dual update, the factored gradient
  * GEMM pair and the primal update; Y is bit-identical to dadmm_forward_stepwise's on guard-free
@@ -237,8 +241,8 @@ int dadmm_forward_tiled(const dadmm_dims* d, const void* op, const float* b,
  * the fused shapes: Grec [K][B][P][n] = the pre-clamp gradient of iteration k (unfolded_DLASSO.py:
  * 73-77) and Urec [K][B][P][n] = U_k entering iteration k; bit-identical to the stepwise recording
  * (dadmm_forward_stepwise with Grec / Urec) on guard-free inputs. Only the streamed single-launch
- * form records: P <= 16, m <= 64, n_pad >= 128 (DADMM_EUNSUPPORTED otherwise: record with
- * dadmm_forward_stepwise). Guards are flagged in `status` as by dadmm_forward_tiled; the gated
+ * form records: P <= 16 at m <= 64 or P <= 8 at m <= 128, n_pad >= 128, whatever DADMM_TILED_STREAM
+ * says (DADMM_EUNSUPPORTED otherwise: record with dadmm_forward_stepwise). Guards are flagged in `status` as by dadmm_forward_tiled; the gated
  * dadmm_forward_stepwise behind it (with the same Grec / Urec) re-records a flagged batch exactly.
  * Replaces: the forward half of loss.backward() through DLASSO_unfolded (unfolded_train_new.py:74-80). */
 int dadmm_forward_tiled_record(const dadmm_dims* d, const void* op, const float* b,
@@ -246,6 +250,16 @@ int dadmm_forward_tiled_record(const dadmm_dims* d, const void* op, const float*
                                const float* hyp, const float* y0, const float* U0, const float* d0,
                                float* Y, float* Grec, float* Urec, float* U_out, int32_t* status,
                                void* scratch, void* stream);
+
+/* Which form dadmm_forward_tiled (record = 0) or dadmm_forward_tiled_record (record != 0) would run
+ * for `d` in the current environment (DADMM_TILED_STREAM, DADMM_STREAM_WAVES): 1 = the streamed
+ * single launch, 0 = the per-iteration launches (also for B = 0 or K = 0, which launch nothing).
+ * A negative DADMM_E* is the code that entry point would return for the shape before launching
+ * (DADMM_EUNSUPPORTED for m > 128, or for record != 0 where the streamed form does not apply);
+ * dadmm_last_error() then holds its text. Asks the predicate the launch itself asks; needs no GPU.
+ * Replaces: nothing in the reference (its one forward serves every shape, unfolded_DLASSO.py:53-109);
+ *           see dadmm_forward_tiled for what the two forms compute. */
+int dadmm_tiled_form(const dadmm_dims* d, int32_t record);
 
 /* Bytes of device scratch dadmm_forward_stepwise needs for `d` (256-byte aligned pointer). */
 size_t dadmm_stepwise_scratch_bytes(const dadmm_dims* d);
