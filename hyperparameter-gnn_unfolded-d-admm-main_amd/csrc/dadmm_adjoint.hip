@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dadmm_consensus.h"
 #include "dadmm_device.h"
 #include "dadmm_internal.h"
 
@@ -31,17 +32,8 @@ constexpr int THREADS = 256;   // 4 waves, one (sample, 64-column) item each
 constexpr int WAVES = 4;
 // the register-resident update runs in the 16-byte-lane form (adj_update_v4)
 
-// sum over p's visit list of (x_p - x_q): compute_delta's accumulation order (:127-140). The
-// sample's list starts vp [P + 1] (relative) and entries vq sit in this wave's LDS slice: the
-// list walk is LDS reads, not a chain of dependent global loads per agent.
-__device__ __forceinline__ float visit_sum(const float* __restrict__ x, const int32_t* __restrict__ vp,
-                                           const uint8_t* __restrict__ vq, int p, int lane) {
-    const float xp = x[p * 64 + lane];
-    float acc = 0.0f;
-    const int t1 = vp[p + 1];
-    for (int t = vp[p]; t < t1; ++t) acc = acc + (xp - x[(int)vq[t] * 64 + lane]);
-    return acc;
-}
+// The sample's visit lists sit in this wave's LDS slice (stage_visits): the list walks (visit_sum,
+// visit_sum4) are LDS reads, not a chain of dependent global loads per agent.
 
 // wave-sum of v into red[p][c] (lane 0 accumulates; one wave owns its red slice) on DPP moves
 // (wave_sum_dpp)
@@ -62,8 +54,7 @@ __global__ __launch_bounds__(64 * W) void adj_update_kernel(AdjArgs a, int k, in
     float* ds = xs + P * 64;                   // [P][64] d_bar (w.r.t. delta_{k+1})
     float* red = lds + WAVES * 2 * P * 64;     // [WAVES][P][4] partial sums
     float* rw = red + w * P * 4;
-    // per wave: the sample's visit-list starts [P + 1] and entries [<= 2 P^2 bytes]
-    int32_t* vpl = (int32_t*)(red + WAVES * P * 4) + w * (P + 1 + (2 * P * P + 3) / 4);
+    int32_t* vpl = (int32_t*)(red + WAVES * P * 4) + w * visit_slice_words(P);   // per wave
     uint8_t* vql = (uint8_t*)(vpl + P + 1);
     for (int i = lane; i < P * 4; i += 64) rw[i] = 0.0f;
     const int item = blockIdx.x * WAVES + w;
@@ -74,16 +65,10 @@ __global__ __launch_bounds__(64 * W) void adj_update_kernel(AdjArgs a, int k, in
         const bool cv = c < n;
         const size_t base = (size_t)s * P * n + (cv ? c : 0);
         const int g0 = a.graph_shared ? 0 : s * P;
-        {
-            const int v0 = a.vptr[g0], ve = a.vptr[g0 + P];
-            for (int i = lane; i <= P; i += 64) vpl[i] = a.vptr[g0 + i] - v0;
-            for (int i = lane; i < ve - v0; i += 64) vql[i] = a.vq[v0 + i];
-        }
+        stage_visits(a.vptr, a.vq, g0, P, vpl, vql, lane, 64);
         float gclip, vclip;
         iter_clips(a.variant, k, gclip, vclip);
-        auto hyp = [&](int kk, int p, int comp) {
-            return a.hyp[((size_t)kk * H + (H == 1 ? 0 : p)) * 4 + comp];
-        };
+        auto hyp = [&](int kk, int p, int comp) { return a.hyp[hyp_index(kk, H, p) + comp]; };
         const float* __restrict__ y1 = a.Y + (size_t)k * S;                    // y_{k+1}
         const float* __restrict__ yk = k > 0 ? a.Y + (size_t)(k - 1) * S : a.y0;
         // restrict-qualified views: the scratch state (yb, Ub, Gb) never aliases the recorded
@@ -122,19 +107,16 @@ __global__ __launch_bounds__(64 * W) void adj_update_kernel(AdjArgs a, int k, in
             for (int i = 0; i < GP; ++i) {
                 const int p = p0 + i;
                 if (p >= P) break;
-                const bool md = a.variant == 0 || inside(d1[i], -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);   // GNN clamp :229
-                const float dcl = a.variant == 0 ? d1[i] : tclamp(d1[i], -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);
                 float pe = 0.0f, db = 0.0f;
                 if (cv) {
                     const size_t off = base + (size_t)p * n;
                     const float et = hyp(k, p, 3);
                     const float rh1 = k + 1 < K ? hyp(k + 1, p, 2) : 0.0f;
                     ybs[off] = yb[i] + gy[i];                                     // + gY[k]
-                    const float wv = ur[i] + dcl * et;
-                    const float wb = inside(wv, -vclip, vclip) ? ub[i] : 0.0f;
-                    pe = wb * dcl;
-                    db = md ? gb[i] * rh1 + wb * et : 0.0f;
-                    Ubs[off] = wb;
+                    const DualAdj da = dual_adj<Clamp::MINMAX>(d1[i], ur[i], et, ub[i], a.variant != 0, vclip);
+                    pe = da.pe;
+                    db = da.md ? gb[i] * rh1 + da.wbe : 0.0f;
+                    Ubs[off] = da.wb;
                 }
                 ds[p * 64 + lane] = db;
                 wave_accum(rw, p, 3, pe, lane);
@@ -175,27 +157,21 @@ __global__ __launch_bounds__(64 * W) void adj_update_kernel(AdjArgs a, int k, in
             for (int i = 0; i < GP; ++i) {
                 const int p = p0 + i;
                 if (p >= P) break;
-                float pa = 0.0f, pt = 0.0f, pr = 0.0f;
+                PrimalAdj pj = {};
                 if (cv) {
                     const size_t off = base + (size_t)p * n;
                     const float al = hyp(k, p, 0);
                     const float y = xs[p * 64 + lane];
-                    const float g = tclamp(gr[i], -gclip, gclip);
-                    const float z = y - al * g;
-                    const float ybv = yb[i] + tv[i];
-                    const float zb = inside(z, -vclip, vclip) ? ybv : 0.0f;
-                    pa = -zb * g;
-                    const float grb = inside(gr[i], -gclip, gclip) ? -al * zb : 0.0f;
-                    pt = grb * sign_times(y, 1.0f);
-                    pr = grb * dk[i];
+                    pj = primal_adj(y, gr[i], grad_clamp<Clamp::MINMAX>(gr[i], gclip), al, yb[i] + tv[i], dk[i], gclip,
+                                    vclip);
                     const float dg = a.deg[g0 + p];
-                    Ubs[off] = ub[i] + grb * dg;
-                    ybs[off] = zb;
-                    Gbs[off] = grb;
+                    Ubs[off] = ub[i] + pj.grb * dg;
+                    ybs[off] = pj.zb;
+                    Gbs[off] = pj.grb;
                 }
-                wave_accum(rw, p, 0, pa, lane);
-                wave_accum(rw, p, 1, pt, lane);
-                wave_accum(rw, p, 2, pr, lane);
+                wave_accum(rw, p, 0, pj.pa, lane);
+                wave_accum(rw, p, 1, pj.pt, lane);
+                wave_accum(rw, p, 2, pj.pr, lane);
             }
         }
     }
@@ -216,18 +192,6 @@ __global__ __launch_bounds__(64 * W) void adj_update_kernel(AdjArgs a, int k, in
 // the LDS rows are read as b128 (a 16-lane group spans 16 distinct 16-byte bank slots). Every
 // element's value and operation order is the generic kernel's; only the dhyp partial sums are
 // associated differently (each lane's 4 columns, then a 16-lane shuffle tree per agent).
-__device__ __forceinline__ f32x4 visit_sum4(const float* __restrict__ x, const int32_t* __restrict__ vp,
-                                             const uint8_t* __restrict__ vq, int p, int cq) {
-    const f32x4 xp = *(const f32x4*)(x + p * 64 + 4 * cq);
-    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-    const int t1 = vp[p + 1];
-    for (int t = vp[p]; t < t1; ++t) {
-        const f32x4 xq = *(const f32x4*)(x + (int)vq[t] * 64 + 4 * cq);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] = acc[r] + (xp[r] - xq[r]);
-    }
-    return acc;
-}
 
 // sum of v over this lane's 4 columns and its 16-lane group -> red[p][c] (lane 16 a adds)
 __device__ __forceinline__ void group_accum(float* red, int p, int c, f32x4 v, bool live, int lane) {
@@ -246,7 +210,7 @@ __global__ __launch_bounds__(THREADS) void adj_update_v4(AdjArgs a, int k, int i
     float* ds = xs + P * 64;
     float* red = lds + WAVES * 2 * P * 64;
     float* rw = red + w * P * 4;
-    int32_t* vpl = (int32_t*)(red + WAVES * P * 4) + w * (P + 1 + (2 * P * P + 3) / 4);
+    int32_t* vpl = (int32_t*)(red + WAVES * P * 4) + w * visit_slice_words(P);
     uint8_t* vql = (uint8_t*)(vpl + P + 1);
     for (int i = lane; i < P * 4; i += 64) rw[i] = 0.0f;
     const int item = blockIdx.x * WAVES + w;
@@ -257,16 +221,10 @@ __global__ __launch_bounds__(THREADS) void adj_update_v4(AdjArgs a, int k, int i
         const int s = item / nch, c = (item % nch) * 64 + 4 * cq;
         const bool cv = c < n;                          // n % 4 == 0: all 4 columns or none
         const int g0 = a.graph_shared ? 0 : s * P;
-        {
-            const int v0 = a.vptr[g0], ve = a.vptr[g0 + P];
-            for (int i = lane; i <= P; i += 64) vpl[i] = a.vptr[g0 + i] - v0;
-            for (int i = lane; i < ve - v0; i += 64) vql[i] = a.vq[v0 + i];
-        }
+        stage_visits(a.vptr, a.vq, g0, P, vpl, vql, lane, 64);
         float gclip, vclip;
         iter_clips(a.variant, k, gclip, vclip);
-        auto hyp = [&](int kk, int p, int comp) {
-            return a.hyp[((size_t)kk * H + (H == 1 ? 0 : p)) * 4 + comp];
-        };
+        auto hyp = [&](int kk, int p, int comp) { return a.hyp[hyp_index(kk, H, p) + comp]; };
         auto off_of = [&](int p) { return (size_t)s * P * n + (size_t)p * n + (cv ? c : 0); };
         const f32x4 z4 = {0.0f, 0.0f, 0.0f, 0.0f};
         auto ld = [&](const float* __restrict__ base, int p) {
@@ -310,20 +268,17 @@ __global__ __launch_bounds__(THREADS) void adj_update_v4(AdjArgs a, int k, int i
             ubr[g] = ld(Ubs, p);
             ybr[g] = ld(ybs, p);
             const bool pv = p < P;
-            const f32x4 d1 = pv ? visit_sum4(xs, vpl, vql, p, cq) : z4;
+            const f32x4 d1 = pv ? visit_sum4<64>(xs, vpl, vql, p, 4 * cq) : z4;
             const float et = hyp(k, pv ? p : 0, 3);
             const float rh1 = k + 1 < K ? hyp(k + 1, pv ? p : 0, 2) : 0.0f;
             f32x4 pe = z4, db = z4;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const bool md = a.variant == 0 || inside(d1[r], -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);   // GNN clamp :229
-                const float dcl = a.variant == 0 ? d1[r] : tclamp(d1[r], -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);
                 ybr[g][r] = ybr[g][r] + gy[r];                                   // + gY[k]
-                const float wv = ur[r] + dcl * et;
-                const float wb = inside(wv, -vclip, vclip) ? ubr[g][r] : 0.0f;
-                pe[r] = wb * dcl;
-                db[r] = md ? gb[r] * rh1 + wb * et : 0.0f;
-                ubr[g][r] = wb;
+                const DualAdj da = dual_adj<Clamp::MINMAX>(d1[r], ur[r], et, ubr[g][r], a.variant != 0, vclip);
+                pe[r] = da.pe;
+                db[r] = da.md ? gb[r] * rh1 + da.wbe : 0.0f;
+                ubr[g][r] = da.wb;
             }
             if (!cv) pe = db = z4;
             if (pv) *(f32x4*)(ds + p * 64 + 4 * cq) = db;
@@ -345,9 +300,9 @@ __global__ __launch_bounds__(THREADS) void adj_update_v4(AdjArgs a, int k, int i
             const int pc = pv ? p : 0;
             const f32x4 gr = grr[g];
             f32x4 dk = k == 0 ? ld(a.d0, p) : z4;
-            const f32x4 tv = pv ? visit_sum4(ds, vpl, vql, p, cq) : z4;
+            const f32x4 tv = pv ? visit_sum4<64>(ds, vpl, vql, p, 4 * cq) : z4;
             if (k > 0 && pv) {
-                dk = visit_sum4(xs, vpl, vql, p, cq);
+                dk = visit_sum4<64>(xs, vpl, vql, p, 4 * cq);
                 if (a.variant != 0) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) dk[r] = tclamp(dk[r], -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);
@@ -359,17 +314,14 @@ __global__ __launch_bounds__(THREADS) void adj_update_v4(AdjArgs a, int k, int i
             f32x4 pa = z4, pt = z4, pr = z4, ubn, zbv, grbv;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float gv = tclamp(gr[r], -gclip, gclip);
-                const float z = y[r] - al * gv;
-                const float ybv = ybr[g][r] + tv[r];
-                const float zb = inside(z, -vclip, vclip) ? ybv : 0.0f;
-                pa[r] = -zb * gv;
-                const float grb = inside(gr[r], -gclip, gclip) ? -al * zb : 0.0f;
-                pt[r] = grb * sign_times(y[r], 1.0f);
-                pr[r] = grb * dk[r];
-                ubn[r] = ubr[g][r] + grb * dg;
-                zbv[r] = zb;
-                grbv[r] = grb;
+                const PrimalAdj pj = primal_adj(y[r], gr[r], grad_clamp<Clamp::MINMAX>(gr[r], gclip), al,
+                                                ybr[g][r] + tv[r], dk[r], gclip, vclip);
+                pa[r] = pj.pa;
+                pt[r] = pj.pt;
+                pr[r] = pj.pr;
+                ubn[r] = ubr[g][r] + pj.grb * dg;
+                zbv[r] = pj.zb;
+                grbv[r] = pj.grb;
             }
             st(Ubs, p, ubn);
             st(ybs, p, zbv);
@@ -392,7 +344,7 @@ __global__ __launch_bounds__(THREADS) void adj_update_v4(AdjArgs a, int k, int i
 }  // namespace adj
 
 static size_t lds_for(int P, int W) {
-    return 4 * ((size_t)W * 2 * P * 64 + (size_t)W * P * 4 + (size_t)W * (P + 1 + (2 * P * P + 3) / 4));
+    return 4 * ((size_t)W * 2 * P * 64 + (size_t)W * P * 4 + (size_t)W * visit_slice_words(P));
 }
 // waves per workgroup of the update kernel: 4, or fewer where four waves' LDS would not fit
 int adjoint_waves(int P) {

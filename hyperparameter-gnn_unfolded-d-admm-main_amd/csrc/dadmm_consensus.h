@@ -2,11 +2,16 @@
 // sample, in the reference's accumulation order (unfolded_DLASSO.py:127-140). Shared by the fused
 // forward and the fused adjoint (which must reproduce the forward's delta bit-for-bit to recover
 // its clamp masks, and applies the same linear map to the adjoint: (2 (D - Adj))^T = 2 (D - Adj)).
+// stage_visits / visit_sum / visit_sum4 at the end are the same sum for the kernels that take any P
+// and per-sample graphs (stepwise, GNN step and step backward, the any-shape adjoint, the tiled
+// consensus): the order is read from the sample's visit lists, staged in LDS, instead of being
+// unrolled over a register-resident graph.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dadmm_device.h"
 #include "dadmm_internal.h"
 
 namespace dadmm {
@@ -244,6 +249,54 @@ __device__ __forceinline__ void consensus_ordered(const float (&yy)[P][E], float
 #pragma unroll
         for (int e = 0; e < E; ++e) dl[p][e] = acc[e];
     }
+}
+
+// ---- the visit-list form: any P, per-sample graphs ------------------------------------------------
+// The kernels that hold no graph in registers (stepwise, GNN step and step backward, the any-shape
+// adjoint, the tiled consensus) read the reference's order from the ingested visit lists: vptr
+// [G P + 1] list starts and vq, one byte per visit, the neighbour q of each `+= (x_p - x_q)` that
+// compute_delta makes on delta[p], in order (both ends of an edge list each other).
+// stage_visits copies sample-graph g0 / P's lists into an LDS slice of visit_slice_words(P)
+// (dadmm_internal.h): starts made relative at vpl [P + 1], entries at vql. Threads tid, tid + nt,
+// ... of the wave or workgroup that owns the slice; the caller synchronises them. entries = false
+// leaves the entries in global memory (the stepwise path's lists past its LDS budget).
+__device__ __forceinline__ void stage_visits(const int32_t* __restrict__ vptr, const uint8_t* __restrict__ vq,
+                                             int g0, int P, int32_t* vpl, uint8_t* vql, int tid, int nt,
+                                             bool entries = true) {
+    const int v0 = vptr[g0], ve = vptr[g0 + P];
+    for (int i = tid; i <= P; i += nt) vpl[i] = vptr[g0 + i] - v0;
+    if (entries)
+        for (int i = tid; i < ve - v0; i += nt) vql[i] = vq[v0 + i];
+}
+// sum over p's visit list of (x_p - x_q), one fp32 add chain from 0 in the list's order, for the
+// lane's column of the rows x [P][64]
+__device__ __forceinline__ float visit_sum(const float* x, const int32_t* vp,
+                                           const uint8_t* vq, int p, int lane) {
+    const float xp = x[p * 64 + lane];
+    float acc = 0.0f;
+    const int t1 = vp[p + 1];
+    for (int t = vp[p]; t < t1; ++t) acc = acc + (xp - x[(int)vq[t] * 64 + lane]);
+    return acc;
+}
+// the same on the lane's four columns col .. col + 3 of rows x [P][RS]. PACKED: whole-vector ops
+// (two v_pk_add_f32 per visit instead of eight scalar instructions, each half rounded exactly as
+// the scalar op), for the sites that have the issue slots
+template <int RS, bool PACKED = false>
+__device__ __forceinline__ f32x4 visit_sum4(const float* __restrict__ x, const int32_t* __restrict__ vp,
+                                            const uint8_t* __restrict__ vq, int p, int col) {
+    const f32x4 xp = *(const f32x4*)(x + p * RS + col);
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+    const int t1 = vp[p + 1];
+    for (int t = vp[p]; t < t1; ++t) {
+        const f32x4 xq = *(const f32x4*)(x + (int)vq[t] * RS + col);
+        if constexpr (PACKED) {
+            acc = acc + (xp - xq);
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[r] = acc[r] + (xp[r] - xq[r]);
+        }
+    }
+    return acc;
 }
 
 template <int P, int GRAPH>

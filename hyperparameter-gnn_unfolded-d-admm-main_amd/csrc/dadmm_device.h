@@ -1,8 +1,8 @@
 // dadmm_device.h — the device-only primitives of the kernel translation units, each stated once:
 // vector / resource / address-space types, MFMA and buffer-memory wrappers, the clamps and guards,
 // the compiler-opacity helpers, the guard-flag atomics, the XCD swizzle, the wave reductions, the
-// reference's per-iteration clip schedule and the element update it feeds. Everything is
-// __forceinline__: no symbol is emitted.
+// reference's per-iteration clip schedule, the element update it feeds and that update's adjoint.
+// Everything is __forceinline__: no symbol is emitted.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -177,6 +177,47 @@ __device__ __forceinline__ void dual_elem(float cons, float eta, float dlim, flo
     D = d;
 }
 
+// ---- the adjoint of the element update -----------------------------------------------------------
+// What torch autograd makes of the lines above (sign() has zero derivative, a clamp passes the
+// gradient where lo <= x <= hi), for the any-shape adjoint (dadmm_adjoint.hip) and the GNN step
+// backward (dadmm_gnn.hip); the masks re-evaluate the forward's own float ops, so the caller
+// passes the forward's clamp. (The fused adjoint, dadmm_backward.hip, keeps its own statement.)
+// Dual update (:95-99), from the raw consensus sum cons = 2 L y_{k+1}, the recorded U_k, eta and
+// the incoming U_bar: d = the delta the forward used (GNN variant: clamped, and md = that clamp
+// passes the gradient, gnn_dlasso_models_progressive.py:229), wb = U_bar through the dual clamp,
+// pe = the eta partial, wbe = wb * eta, the dual update's own term of d_bar: the caller adds what
+// else reaches delta_{k+1} and applies md.
+struct DualAdj {
+    float d, wb, pe, wbe;
+    bool md;
+};
+template <Clamp C>
+__device__ __forceinline__ DualAdj dual_adj(float cons, float u, float eta, float ubar, bool gnn, float vclip) {
+    DualAdj r;
+    r.md = !gnn || inside(cons, -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT);
+    r.d = gnn ? delta_clamp<C>(cons, GNN_DELTA_LIMIT) : cons;
+    r.wb = inside(u + r.d * eta, -vclip, vclip) ? ubar : 0.0f;
+    r.pe = r.wb * r.d;
+    r.wbe = r.wb * eta;
+    return r;
+}
+// Primal update and gradient clamp (:73-93), from y_k, the pre-clamp gradient gr, g = its clamp as
+// the forward took it, the incoming y_bar and delta_k: zb = y_bar through the value clamp, grb =
+// the adjoint of gr, and the alpha, tau and rho partials
+struct PrimalAdj {
+    float zb, grb, pa, pt, pr;
+};
+__device__ __forceinline__ PrimalAdj primal_adj(float y, float gr, float g, float alpha, float ybar, float dk,
+                                                float gclip, float vclip) {
+    PrimalAdj r;
+    r.zb = inside(y - alpha * g, -vclip, vclip) ? ybar : 0.0f;
+    r.pa = -r.zb * g;
+    r.grb = inside(gr, -gclip, gclip) ? -alpha * r.zb : 0.0f;
+    r.pt = r.grb * sign_times(y, 1.0f);
+    r.pr = r.grb * dk;
+    return r;
+}
+
 // ---- compiler opacity --------------------------------------------------------------------------
 // A per-iteration opaque copy of a loop-invariant offset: keeps `base + constant` inside the loop
 // so instruction selection folds the constant into the load's immediate offset instead of LICM
@@ -206,9 +247,14 @@ __device__ __forceinline__ void flag_or(int32_t* f, bool v) {
 
 // ---- the hyper-parameter table of the on-chip forwards (fused, role-split, column-split) --------
 // seq_hyp(k) row p: (alpha, tau, rho, eta), kernel-uniform scalars through the scalar cache
+// hyp [K][H][4]: the row of agent p (H = 1: one row for all agents), and where seq_hyp(k)'s starts
+__device__ __forceinline__ int hyp_agent_row(int H, int p) { return H == 1 ? 0 : p; }
+__device__ __forceinline__ size_t hyp_index(int k, int H, int p) {
+    return ((size_t)k * H + hyp_agent_row(H, p)) * 4;
+}
 __device__ __forceinline__ void load_hyp_row(const FusedArgs& a, int k, int p, float& al, float& ta,
                                              float& rh, float& et) {
-    const cfloat* hp = (const cfloat*)a.hyp + ((size_t)k * a.hyp_rows + (a.hyp_rows == 1 ? 0 : p)) * 4;
+    const cfloat* hp = (const cfloat*)a.hyp + hyp_index(k, a.hyp_rows, p);
     al = hp[0]; ta = hp[1]; rh = hp[2]; et = hp[3];
 }
 

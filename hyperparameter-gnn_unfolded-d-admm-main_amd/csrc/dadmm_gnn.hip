@@ -33,6 +33,7 @@
 
 #include <type_traits>
 
+#include "dadmm_consensus.h"
 #include "dadmm_device.h"
 #include "dadmm_internal.h"
 
@@ -64,7 +65,7 @@ __device__ __forceinline__ const float* y_source(const GnnArgs& a, int k, bool& 
 
 // hyp_k of sample s, agent p, component c (alpha, tau, rho, eta): [B][4][H] (view(B, 4, P|1))
 __device__ __forceinline__ float hyp_at(const GnnArgs& a, int s, int c, int p) {
-    return a.hyp[((size_t)s * 4 + c) * a.hyp_rows + (a.hyp_rows == 1 ? 0 : p)];
+    return a.hyp[((size_t)s * 4 + c) * a.hyp_rows + hyp_agent_row(a.hyp_rows, p)];
 }
 
 // ---- zero: the guard flag words (a kernel, not hipMemsetAsync: the inference forward is captured
@@ -506,11 +507,9 @@ static_assert(UCB == 64 || UCB == 128, "UCB");
 // Keeping phase 1's U rows in registers for phase 2 (one fewer HBM stream) was measured and
 // dropped: 97 instead of 82 VGPRs, four instead of five waves per SIMD, 86.1-86.4 vs 84.7-85.0 ms
 // at the configs[4] shard forward (profiles/r04/variants_r04o_step_keepu.txt)
-// LDS bytes for one sample's visit lists: at most 2 P entries per agent (each incident edge is
-// visited from both of its ends; a self-loop twice), one byte each
-__host__ __device__ constexpr int update_visit_words(int P) { return (2 * P * P + 3) / 4; }
+// the y_{k+1} rows [P][UCB], then the sample's visit lists
 __host__ __device__ constexpr size_t update_lds_bytes(int P) {
-    return 4 * ((size_t)P * UCB + (size_t)(P + 1) + update_visit_words(P));
+    return 4 * ((size_t)P * UCB + (size_t)visit_slice_words(P));
 }
 template <bool FUSED>
 __device__ __forceinline__ void update_item(const GnnArgs& a, int k, int item, float* lds) {
@@ -542,9 +541,7 @@ __device__ __forceinline__ void update_item(const GnnArgs& a, int k, int item, f
     int32_t* vpl = (int32_t*)(yl + P * UCB);          // [P + 1] list starts (sample-local)
     uint8_t* vl = (uint8_t*)(vpl + P + 1);            // the sample's visit lists
     const int g0 = a.graph_shared ? 0 : s * P;
-    const int vb = a.vptr[g0], vlen = a.vptr[g0 + P] - vb;
-    for (int i = threadIdx.x; i <= P; i += THREADS) vpl[i] = a.vptr[g0 + i] - vb;
-    for (int i = threadIdx.x; i < vlen; i += THREADS) vl[i] = a.vq[vb + i];
+    stage_visits(a.vptr, a.vq, g0, P, vpl, vl, threadIdx.x, THREADS);
     const float* __restrict__ U = a.U;
     float* __restrict__ Yk = a.yptr[k + 1];
     const f32x4 z4 = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -649,15 +646,7 @@ __device__ __forceinline__ void update_item(const GnnArgs& a, int k, int item, f
         for (int u = 0; u < UP_CH; ++u) {
             const int p = RPI * (q0 + WAVES * u) + half;
             if (p >= P || !cv) continue;
-            const f32x4 yp = *(const f32x4*)(yl + p * UCB + cl);
-            f32x4 acc = z4;
-            const int v0 = vpl[p], v1 = vpl[p + 1];
-            // whole-vector ops: two v_pk_add_f32 / v_pk_add_f32(neg) per visit instead of eight
-            // scalar instructions, each lane of the pair rounded exactly as the scalar op
-            for (int t = v0; t < v1; ++t) {
-                const f32x4 yq = *(const f32x4*)(yl + (int)vl[t] * UCB + cl);
-                acc = acc + (yp - yq);
-            }
+            f32x4 acc = visit_sum4<UCB, true>(yl, vpl, vl, p, cl);   // packed adds
             const float et = FUSED ? etv[u] : hyp_at(a, s, 3, p);
             f32x4 un;
 #pragma unroll
@@ -738,13 +727,17 @@ __global__ __launch_bounds__(THREADS) void finish_kernel(GnnArgs a) {
 // wave waits for memory once per chunk instead of once per agent and phase (the per-agent loads of
 // the loop form serialised ~10 HBM round trips: 22 us per iteration at B = 256). The same
 // operations in the same order as the loop form: bit-identical.
+// floats per wave: three [P][64] row blocks, the per-sample hyp gradient [4][P], the visit lists
+__host__ __device__ constexpr int step_backward_slice_words(int P) {
+    return 3 * P * 64 + 4 * P + visit_slice_words(P);
+}
 template <int PR>
 __global__ __launch_bounds__(THREADS) void step_backward_kernel(GnnArgs a, int k, GnnGrads gg) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int P = a.P, n = a.n, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int H = a.hyp_rows;
-    const int VW = (P + 1) + (2 * P * P + 3) / 4;   // visit-list words per wave
-    float* sl = lds + wv * (3 * P * 64 + 4 * P + VW);
+    const int SW = step_backward_slice_words(P);   // floats per wave slice
+    float* sl = lds + wv * SW;
     float* y1l = sl;                           // [P][64] y_{k+1}
     float* dbl = sl + P * 64;                  // [P][64] d_bar_raw
     float* ybl = sl + 2 * P * 64;              // [P][64] 2 L d_bar_raw
@@ -757,16 +750,23 @@ __global__ __launch_bounds__(THREADS) void step_backward_kernel(GnnArgs a, int k
     const float* ys = a.yk;
     const int g0 = a.graph_shared ? 0 : s * P;
     for (int i = lane; i < 4 * H; i += 64) red[i] = 0.0f;
-    {
-        const int v0 = a.vptr[g0], ve = a.vptr[g0 + P];
-        for (int i = lane; i <= P; i += 64) vpl[i] = a.vptr[g0 + i] - v0;
-        for (int i = lane; i < ve - v0; i += 64) vql[i] = a.vq[v0 + i];
-    }
+    stage_visits(a.vptr, a.vq, g0, P, vpl, vql, lane, 64);
     __builtin_amdgcn_wave_barrier();
     auto accum = [&](int c, int p, float v) {   // wave-sum v into red[c][p or 0]
         v = wave_sum_dpp(v);
-    
-        if (lane == 0) red[c * H + (H == 1 ? 0 : p)] += v;
+        if (lane == 0) red[c * H + hyp_agent_row(H, p)] += v;
+    };
+    // The forward of agent p recomputed from its operands with the step's own ops (update_item):
+    // the pre-clamp gradient gr and its clamp g; y_{k+1} = primal_y(y, alpha, g). The adjoint's
+    // masks are only right if these are the forward's bits.
+    struct Fwd {
+        float gr, g;
+    };
+    auto forward = [&](int p, float y, float AtAy, float Atb, float U, float D) {
+        Fwd f;
+        f.gr = grad_assemble(AtAy - Atb, y, U, D, hyp_at(a, s, 1, p), a.deg[g0 + p], hyp_at(a, s, 2, p));
+        f.g = grad_clamp<Clamp::NANPROP>(f.gr, gclip);
+        return f;
     };
     // (round 4) no-alias views of the streams, so that the unrolled agent loops below can put
     // several agents' loads in flight together; the loads read column min(c, n - 1) (always a
@@ -798,80 +798,48 @@ __global__ __launch_bounds__(THREADS) void step_backward_kernel(GnnArgs a, int k
 #pragma unroll
             for (int p = 0; p < PR; ++p) {
                 if (p >= P) break;
-                const float y = ry[p];
-                const float ta = hyp_at(a, s, 1, p);
-                const float st = sign_times(y, ta);
-                float gr = rA[p] - rB[p];
-                gr = gr + st;
-                gr = gr + rU[p] * a.deg[g0 + p];
-                gr = gr + rD[p] * hyp_at(a, s, 2, p);
-                const float g = clamp_t(gr, -gclip, gclip);
-                const float y1 = clamp_t(y - hyp_at(a, s, 0, p) * g, -vclip, vclip);
+                const Fwd f = forward(p, ry[p], rA[p], rB[p], rU[p], rD[p]);
+                const float y1 = primal_y<Clamp::NANPROP>(ry[p], hyp_at(a, s, 0, p), f.g, vclip);
                 y1l[p * 64 + lane] = cv ? y1 : 0.0f;
             }
             // dual update adjoint; d_bar_raw (w.r.t. 2 L y_{k+1} before the GNN clamp)
 #pragma unroll
             for (int p = 0; p < PR; ++p) {
                 if (p >= P) break;
-                const float yp = y1l[p * 64 + lane];
-                float acc = 0.0f;
-                const int t1 = vpl[p + 1];
-                for (int t = vpl[p]; t < t1; ++t) acc = acc + (yp - y1l[(int)vql[t] * 64 + lane]);
-                float dbr = 0.0f, pe = 0.0f;
-                rwb[p] = 0.0f;
+                const float acc = visit_sum(y1l, vpl, vql, p, lane);
+                DualAdj da = {};
+                float dbr = 0.0f;
                 if (cv) {
-                    const float d1 = a.variant != 0 ? clamp_t(acc, -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT) : acc;
-                    const float et = hyp_at(a, s, 3, p);
-                    const float wvv = rU[p] + d1 * et;
-                    const float wb = (gg.gU1 != nullptr && inside(wvv, -vclip, vclip)) ? rgU1[p] : 0.0f;
-                    pe = wb * d1;
-                    const float db = (gg.gd1 != nullptr ? rgd1[p] : 0.0f) + wb * et;
-                    dbr = (a.variant == 0 || inside(acc, -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT)) ? db : 0.0f;
-                    rwb[p] = wb;
+                    da = dual_adj<Clamp::NANPROP>(acc, rU[p], hyp_at(a, s, 3, p), rgU1[p], a.variant != 0, vclip);
+                    dbr = da.md ? rgd1[p] + da.wbe : 0.0f;
                 }
-                accum(3, p, pe);
+                rwb[p] = da.wb;
+                accum(3, p, da.pe);
                 dbl[p * 64 + lane] = dbr;
             }
 #pragma unroll
             for (int p = 0; p < PR; ++p) {   // 2 L d_bar_raw, same visit lists (the map is symmetric)
                 if (p >= P) break;
-                const float xp = dbl[p * 64 + lane];
-                float acc = 0.0f;
-                const int t1 = vpl[p + 1];
-                for (int t = vpl[p]; t < t1; ++t) acc = acc + (xp - dbl[(int)vql[t] * 64 + lane]);
-                ybl[p * 64 + lane] = acc;
+                ybl[p * 64 + lane] = visit_sum(dbl, vpl, vql, p, lane);
             }
             // primal update + gradient clamp adjoint
 #pragma unroll
             for (int p = 0; p < PR; ++p) {
                 if (p >= P) break;
-                float pa = 0.0f, pt = 0.0f, pr = 0.0f;
+                PrimalAdj pj = {};
                 if (cv) {
                     const size_t off = base + (size_t)p * n;
-                    const float al = hyp_at(a, s, 0, p), ta = hyp_at(a, s, 1, p), rh = hyp_at(a, s, 2, p);
-                    const float y = ry[p];
-                    const float sg = sign_times(y, 1.0f);
-                    const float st = sign_times(y, ta);
-                    float gr = rA[p] - rB[p];
-                    gr = gr + st;
-                    gr = gr + rU[p] * a.deg[g0 + p];
-                    gr = gr + rD[p] * rh;
-                    const float g = clamp_t(gr, -gclip, gclip);
-                    const float z = y - al * g;
-                    const float yb = (gg.gy1 != nullptr ? rgy1[p] : 0.0f) + ybl[p * 64 + lane];
-                    const float zb = inside(z, -vclip, vclip) ? yb : 0.0f;
-                    pa = -zb * g;
-                    const float grb = inside(gr, -gclip, gclip) ? -al * zb : 0.0f;
-                    pt = grb * sg;
-                    pr = grb * rD[p];
-                    gg.gy[off] = zb;
-                    gg.gU[off] = rwb[p] + grb * a.deg[g0 + p];
-                    gg.gd[off] = grb * rh;
-                    gg.gAtAy[off] = grb;
+                    const Fwd f = forward(p, ry[p], rA[p], rB[p], rU[p], rD[p]);
+                    const float yb = rgy1[p] + ybl[p * 64 + lane];
+                    pj = primal_adj(ry[p], f.gr, f.g, hyp_at(a, s, 0, p), yb, rD[p], gclip, vclip);
+                    gg.gy[off] = pj.zb;
+                    gg.gU[off] = rwb[p] + pj.grb * a.deg[g0 + p];
+                    gg.gd[off] = pj.grb * hyp_at(a, s, 2, p);
+                    gg.gAtAy[off] = pj.grb;
                 }
-                accum(0, p, pa);
-                accum(1, p, pt);
-                accum(2, p, pr);
+                accum(0, p, pj.pa);
+                accum(1, p, pj.pt);
+                accum(2, p, pj.pr);
             }
         }
     } else {
@@ -884,78 +852,49 @@ __global__ __launch_bounds__(THREADS) void step_backward_kernel(GnnArgs a, int k
             for (int p = 0; p < P; ++p) {
                 const size_t off = base + (size_t)p * n;
                 const float y = ys_r[off];
-                const float ta = hyp_at(a, s, 1, p);
-                const float st = sign_times(y, ta);
-                float gr = AtAy_r[off] - Atb_r[off];
-                gr = gr + st;
-                gr = gr + U_r[off] * a.deg[g0 + p];
-                gr = gr + D_r[off] * hyp_at(a, s, 2, p);
-                const float g = clamp_t(gr, -gclip, gclip);
-                const float y1 = clamp_t(y - hyp_at(a, s, 0, p) * g, -vclip, vclip);
+                const Fwd f = forward(p, y, AtAy_r[off], Atb_r[off], U_r[off], D_r[off]);
+                const float y1 = primal_y<Clamp::NANPROP>(y, hyp_at(a, s, 0, p), f.g, vclip);
                 y1l[p * 64 + lane] = cv ? y1 : 0.0f;
             }
             // dual update adjoint; d_bar_raw (w.r.t. 2 L y_{k+1} before the GNN clamp)
             for (int p = 0; p < P; ++p) {
-                const float yp = y1l[p * 64 + lane];
-                float acc = 0.0f;
-                const int t1 = vpl[p + 1];
-                for (int t = vpl[p]; t < t1; ++t) acc = acc + (yp - y1l[(int)vql[t] * 64 + lane]);
-                float dbr = 0.0f, pe = 0.0f;
+                const float acc = visit_sum(y1l, vpl, vql, p, lane);
+                DualAdj da = {};
+                float dbr = 0.0f;
                 if (cv) {
                     const size_t off = base + (size_t)p * n;
-                    const float d1 = a.variant != 0 ? clamp_t(acc, -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT) : acc;
-                    const float et = hyp_at(a, s, 3, p);
-                    const float wvv = a.U[off] + d1 * et;
-                    const float wb = (gg.gU1 != nullptr && inside(wvv, -vclip, vclip)) ? gg.gU1[off] : 0.0f;
-                    pe = wb * d1;
-                    const float db = (gg.gd1 != nullptr ? gg.gd1[off] : 0.0f) + wb * et;
-                    dbr = (a.variant == 0 || inside(acc, -GNN_DELTA_LIMIT, GNN_DELTA_LIMIT)) ? db : 0.0f;
-                    gg.gU[off] = wb;
+                    da = dual_adj<Clamp::NANPROP>(acc, a.U[off], hyp_at(a, s, 3, p),
+                                                  gg.gU1 != nullptr ? gg.gU1[off] : 0.0f, a.variant != 0, vclip);
+                    dbr = da.md ? (gg.gd1 != nullptr ? gg.gd1[off] : 0.0f) + da.wbe : 0.0f;
+                    gg.gU[off] = da.wb;
                 }
-                accum(3, p, pe);
+                accum(3, p, da.pe);
                 dbl[p * 64 + lane] = dbr;
             }
             for (int p = 0; p < P; ++p) {   // 2 L d_bar_raw, same visit lists (the map is symmetric)
-                const float xp = dbl[p * 64 + lane];
-                float acc = 0.0f;
-                const int t1 = vpl[p + 1];
-                for (int t = vpl[p]; t < t1; ++t) acc = acc + (xp - dbl[(int)vql[t] * 64 + lane]);
-                ybl[p * 64 + lane] = acc;
+                ybl[p * 64 + lane] = visit_sum(dbl, vpl, vql, p, lane);
             }
             // primal update + gradient clamp adjoint
             for (int p = 0; p < P; ++p) {
-                float pa = 0.0f, pt = 0.0f, pr = 0.0f;
+                PrimalAdj pj = {};
                 if (cv) {
                     const size_t off = base + (size_t)p * n;
-                    const float al = hyp_at(a, s, 0, p), ta = hyp_at(a, s, 1, p), rh = hyp_at(a, s, 2, p);
                     const float y = ys[off];
-                    const float sg = sign_times(y, 1.0f);
-                    const float st = sign_times(y, ta);
-                    float gr = a.AtAy[off] - a.Atb[off];
-                    gr = gr + st;
-                    gr = gr + a.U[off] * a.deg[g0 + p];
-                    gr = gr + a.D[off] * rh;
-                    const float g = clamp_t(gr, -gclip, gclip);
-                    const float z = y - al * g;
+                    const Fwd f = forward(p, y, a.AtAy[off], a.Atb[off], a.U[off], a.D[off]);
                     const float yb = (gg.gy1 != nullptr ? gg.gy1[off] : 0.0f) + ybl[p * 64 + lane];
-                    const float zb = inside(z, -vclip, vclip) ? yb : 0.0f;
-                    pa = -zb * g;
-                    const float grb = inside(gr, -gclip, gclip) ? -al * zb : 0.0f;
-                    pt = grb * sg;
-                    pr = grb * a.D[off];
-                    gg.gy[off] = zb;
-                    gg.gU[off] = gg.gU[off] + grb * a.deg[g0 + p];
-                    gg.gd[off] = grb * rh;
-                    gg.gAtAy[off] = grb;
+                    pj = primal_adj(y, f.gr, f.g, hyp_at(a, s, 0, p), yb, a.D[off], gclip, vclip);
+                    gg.gy[off] = pj.zb;
+                    gg.gU[off] = gg.gU[off] + pj.grb * a.deg[g0 + p];
+                    gg.gd[off] = pj.grb * hyp_at(a, s, 2, p);
+                    gg.gAtAy[off] = pj.grb;
                 }
-                accum(0, p, pa);
-                accum(1, p, pt);
-                accum(2, p, pr);
+                accum(0, p, pj.pa);
+                accum(1, p, pj.pt);
+                accum(2, p, pj.pr);
             }
         }
     }
     __syncthreads();
-    const int SW = 3 * P * 64 + 4 * P + VW;     // floats per wave slice
     for (int i = threadIdx.x; i < 4 * H; i += THREADS) {
         const float* r0 = lds + 3 * P * 64 + i;
         const size_t idx = (size_t)s * 4 * H + i;
@@ -1086,7 +1025,7 @@ hipError_t gnn_launch_finish(const GnnArgs& a, hipStream_t st) {
 }
 
 hipError_t gnn_launch_step_backward(const GnnArgs& a, int k, const GnnGrads& gg, hipStream_t st) {
-    const size_t lds = 4 * (size_t)gnn::WAVES * (3 * a.P * 64 + 4 * a.P + (a.P + 1) + (2 * a.P * a.P + 3) / 4);
+    const size_t lds = 4 * (size_t)gnn::WAVES * gnn::step_backward_slice_words(a.P);
     if (lds > 160 * 1024) return hipErrorInvalidConfiguration;
     if (lds > 64 * 1024) {
         for (const void* f : {(const void*)gnn::step_backward_kernel<8>, (const void*)gnn::step_backward_kernel<0>}) {

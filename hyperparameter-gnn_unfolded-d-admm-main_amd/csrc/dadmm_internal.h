@@ -16,6 +16,27 @@ constexpr int M_MAX = 1024;  // rows per agent accepted by the ABI (the stepwise
 __host__ __device__ constexpr int m_pad_of(int m) { return (m + M_PAD - 1) / M_PAD * M_PAD; }
 constexpr int FUSED_WAVES = 8;  // waves per workgroup of the fused kernel
 
+// ---- one sample's visit lists in LDS (dadmm_consensus.h stage_visits) ---------------------------
+// The slice the any-shape kernels carve per wave or per workgroup and their launchers size: the
+// list starts [P + 1] (32-bit, relative to the sample's first entry), then the entries, one byte
+// each, rounded up to words. A sample has at most 2 P entries per agent (each incident edge is
+// visited from both of its ends; a self-loop twice): 2 P^2 bytes for a complete graph.
+__host__ __device__ constexpr int visit_slice_words(int P) { return (P + 1) + (2 * P * P + 3) / 4; }
+// The stepwise path caps a wave's entries at 4 KB (always enough for P <= 45, for sparse graphs
+// far beyond); longer lists stay in global memory
+__host__ __device__ constexpr int sw_vcap(int P) {
+    return ((2 * P * P < 4096 ? 2 * P * P : 4096) + 3) & ~3;
+}
+__host__ __device__ constexpr int sw_visit_slice_words(int P) { return (P + 1) + sw_vcap(P) / 4; }
+static_assert(visit_slice_words(1) == 3 && visit_slice_words(5) == 19 && visit_slice_words(45) == 1059 &&
+                  visit_slice_words(46) == 1105 && visit_slice_words(64) == 2113 &&
+                  visit_slice_words(160) == 12961,
+              "visit_slice_words: (P + 1) + ceil(2 P^2 / 4)");
+static_assert(sw_visit_slice_words(1) == 3 && sw_visit_slice_words(5) == 19 &&
+                  sw_visit_slice_words(45) == 1059 && sw_visit_slice_words(46) == 1071 &&
+                  sw_visit_slice_words(64) == 1089 && sw_visit_slice_words(160) == 1185,
+              "sw_visit_slice_words: the same up to P = 45, then (P + 1) + 1024");
+
 // Arguments of the fused kernel (device pointers; see include/dadmm.h for the layouts).
 struct FusedArgs {
     const float* A;      // prepared operator: [P][M_PAD][n_pad]

@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dadmm_consensus.h"
 #include "dadmm_device.h"
 #include "dadmm_internal.h"
 
@@ -37,11 +38,8 @@ namespace {
 
 constexpr int SW_THREADS = 256;   // 4 waves
 constexpr int SW_WAVES = 4;
-// per-wave LDS bytes for a sample's visit lists: the worst case 2 P^2 (a complete graph) up to
-// 4 KB; longer lists are read from global memory (P > 45 with dense graphs)
-__host__ __device__ constexpr int sw_vcap(int P) {
-    return ((2 * P * P < 4096 ? 2 * P * P : 4096) + 3) & ~3;
-}
+// per-wave LDS for a sample's visit lists: sw_visit_slice_words (dadmm_internal.h), entries up to
+// sw_vcap = 4 KB; longer lists are read from global memory (P > 45 with dense graphs)
 
 // iteration k's y_k: Y[j] for the last j < k whose y_next passed the guard, else y0 (zeros when
 // the k = 0 guard fired)
@@ -58,7 +56,7 @@ __device__ __forceinline__ const float* y_source(const StepArgs& a, int k, bool&
 
 __device__ __forceinline__ void hyp_row(const StepArgs& a, int k, int p, float& al, float& ta,
                                         float& rh, float& et) {
-    const float* h = a.hyp + ((size_t)k * a.hyp_rows + (a.hyp_rows == 1 ? 0 : p)) * 4;
+    const float* h = a.hyp + hyp_index(k, a.hyp_rows, p);
     al = h[0]; ta = h[1]; rh = h[2]; et = h[3];
 }
 
@@ -195,16 +193,14 @@ __device__ void phase_update(const StepArgs& a, int k, int item, float* ylds) {
     float* yl = ylds + (threadIdx.x >> 6) * (P * 64);   // this wave's [P][64] y_next
     const int lane = threadIdx.x & 63;
     // this wave's copy of the sample's visit lists: starts [P + 1] (relative), entries (bytes)
-    int32_t* vpl = (int32_t*)(ylds + SW_WAVES * P * 64) + (threadIdx.x >> 6) * (P + 1 + sw_vcap(P) / 4);
+    int32_t* vpl = (int32_t*)(ylds + SW_WAVES * P * 64) + (threadIdx.x >> 6) * sw_visit_slice_words(P);
     uint8_t* vql = (uint8_t*)(vpl + P + 1);
     const int g0 = a.graph_shared ? 0 : s * P;
     const int v0 = a.vptr[g0], ve = a.vptr[g0 + P];
     // the sample's lists in LDS when they fit the per-wave budget (always for P <= 45; sparse
     // graphs far beyond), else read from global memory (many agents, dense graphs)
     const bool vl = ve - v0 <= sw_vcap(P);
-    for (int i = lane; i <= P; i += 64) vpl[i] = a.vptr[g0 + i] - v0;
-    if (vl)
-        for (int i = lane; i < ve - v0; i += 64) vql[i] = a.vq[v0 + i];
+    stage_visits(a.vptr, a.vq, g0, P, vpl, vql, lane, 64, vl);
 
     bool bad_y = false;
     for (int p = 0; p < P; ++p) {
@@ -227,15 +223,9 @@ __device__ void phase_update(const StepArgs& a, int k, int item, float* ylds) {
     for (int p = 0; p < P; ++p) {
         float al, ta, rh, et;
         hyp_row(a, k, p, al, ta, rh, et);
-        const float yp = yl[p * 64 + lane];
-        float acc = 0.0f;
-        const int t1 = vpl[p + 1];
-        if (vl) {
-            for (int t = vpl[p]; t < t1; ++t) acc = acc + (yp - yl[(int)vql[t] * 64 + lane]);
-        } else {
-            const uint8_t* __restrict__ vg = a.vq + v0;
-            for (int t = vpl[p]; t < t1; ++t) acc = acc + (yp - yl[(int)vg[t] * 64 + lane]);
-        }
+        float acc;
+        if (vl) acc = visit_sum(yl, vpl, vql, p, lane);
+        else acc = visit_sum(yl, vpl, a.vq + v0, p, lane);
         if (a.variant != 0) acc = delta_clamp<Clamp::NANPROP>(acc, GNN_DELTA_LIMIT);
         if (cv) {
             const size_t off = base + (size_t)p * n;
@@ -378,7 +368,7 @@ out:
 
 size_t grad_lds_bytes(int n_pad, int m_pad) { return 4 * (size_t)(BT * (n_pad + 4) + BT * (m_pad + 4)); }
 size_t update_lds_bytes(int P) {
-    return 4 * ((size_t)SW_WAVES * P * 64 + (size_t)SW_WAVES * (P + 1 + sw_vcap(P) / 4));
+    return 4 * ((size_t)SW_WAVES * P * 64 + (size_t)SW_WAVES * sw_visit_slice_words(P));
 }
 
 }  // namespace

@@ -25,6 +25,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "dadmm_consensus.h"
 #include "dadmm_device.h"
 #include "dadmm_internal.h"
 
@@ -382,8 +383,8 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(2))) vo
 // pass over y_k), then wave w forms agent p = w, w + 4, ... by its visit list in the reference's
 // order, one fp32 add chain per column from 0 (bit-identical to the fused / stepwise consensus).
 constexpr int CB = 256;
-// visit entries per sample: every node lists each neighbour twice (both ends of an edge), <= 2 P^2
-size_t consensus_lds_bytes(int P) { return 4 * (size_t)P * CB + 4 * (size_t)(P + 1) + 2 * (size_t)P * P; }
+// the sample's rows [P][CB], then its visit lists
+size_t consensus_lds_bytes(int P) { return 4 * ((size_t)P * CB + (size_t)visit_slice_words(P)); }
 __global__ __launch_bounds__(THREADS) void consensus_kernel(TiledArgs a, const float* __restrict__ y) {
     extern __shared__ __attribute__((aligned(16))) float ys[];   // [P][CB]
     const int P = a.P, n = a.n;
@@ -416,23 +417,12 @@ __global__ __launch_bounds__(THREADS) void consensus_kernel(TiledArgs a, const f
         const int p = idx / (CB / 4), c = c0 + 4 * (idx % (CB / 4));
         if (c < n) *(f32x4*)(ys + p * CB + (c - c0)) = *(const f32x4*)(ys_g + (size_t)p * n + c);
     }
-    const int g0 = a.graph_shared ? 0 : s * P;
-    const int vbase = a.vptr[g0], vend = a.vptr[g0 + P];
-    for (int i = threadIdx.x; i <= P; i += THREADS) vp[i] = a.vptr[g0 + i] - vbase;
-    for (int i = threadIdx.x; i < vend - vbase; i += THREADS) vq[i] = a.vq[vbase + i];
+    stage_visits(a.vptr, a.vq, a.graph_shared ? 0 : s * P, P, vp, vq, threadIdx.x, THREADS);
     __syncthreads();
     const int c = c0 + 4 * lane;
     if (c >= n) return;
     for (int p = w; p < P; p += WAVES) {
-        const int v0 = vp[p], v1 = vp[p + 1];
-        const f32x4 yp = *(const f32x4*)(ys + p * CB + 4 * lane);
-        f32x4 dv = {0.0f, 0.0f, 0.0f, 0.0f};
-        for (int t = v0; t < v1; ++t) {
-            const f32x4 yq = *(const f32x4*)(ys + (int)vq[t] * CB + 4 * lane);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dv[r] = dv[r] + (yp[r] - yq[r]);
-        }
-        *(f32x4*)(a.delta + ((size_t)s * P + p) * n + c) = dv;
+        *(f32x4*)(a.delta + ((size_t)s * P + p) * n + c) = visit_sum4<CB>(ys, vp, vq, p, 4 * lane);
     }
 }
 
@@ -545,15 +535,14 @@ __global__ __launch_bounds__(THREADS) void colupdate_kernel(TiledArgs a, int k, 
     for (int ai = 0; ai < AMAX; ++ai) {
         const int p = w + WAVES * ai;
         if (p >= P) break;
-        const int hp = H == 1 ? 0 : p;
         float al = 0, ta = 0, rh = 0, et_prev = 0;
         if (!final_only) {
-            const float* hk = a.hyp + ((size_t)k * H + hp) * 4;
+            const float* hk = a.hyp + hyp_index(k, H, p);
             al = hk[0]; ta = hk[1]; rh = hk[2];
             const float et = hk[3];
             status |= (finitef(al) && finitef(ta) && finitef(rh) && finitef(et)) ? 0 : DADMM_STATUS_YNEXT_NAN;
         }
-        if (k > 0) et_prev = a.hyp[((size_t)(k - 1) * H + hp) * 4 + 3];
+        if (k > 0) et_prev = a.hyp[hyp_index(k - 1, H, p) + 3];
         // every global operand of this agent is issued first (R_p, A_p^T rows, U_{k-1}, d0); the
         // consensus over the LDS block runs under their latency
         f32x4 rv[HALVES][TM], at[NT][TM], up[NT][HALVES], dv[NT][HALVES], yv[NT][HALVES];

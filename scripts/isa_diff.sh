@@ -3,7 +3,9 @@
 # Compiles every csrc/*.hip (and the two recording builds) of REV, from a temporary git worktree,
 # and of the working tree to device assembly with the Makefile's flags, and diffs them file by
 # file. Only the translation-unit id __hip_cuid_<hex> (a hash of the source text) is erased.
-# Prints `identical` or the first lines of the diff per file; exit status 1 if any file differs.
+# Prints `identical` or the first lines of the diff per file, and for a file that differs one line
+# per kernel with both sides' instruction-line count and register / spill / LDS / scratch metadata;
+# exit status 1 if any file differs.
 set -euo pipefail
 REV=${1:?usage: isa_diff.sh REV}
 ROOT=$(git -C "$(dirname "$0")" rev-parse --show-toplevel)
@@ -22,10 +24,37 @@ mkdir "$TMP/a" "$TMP/b"
     xargs -P "${JOBS:-16}" -L 1 bash -c \
         '$0 $4 -x hip --cuda-device-only -S "$3" -o "$1/$2.s" 2>"$1/$2.err" || { cat "$1/$2.err"; rm -f "$1/$2.s"; }' "$FLAGS"
 norm() { sed -E 's/__hip_cuid_[0-9a-f]+/__hip_cuid/g' "$1"; }
+# "kernel insts vgpr sgpr vgpr_spill sgpr_spill lds scratch" per kernel of the assembly file $1:
+# the instruction lines between the kernel's label and its .Lfunc_end, and the code object
+# metadata's register, spill, LDS (.group_segment_fixed_size) and scratch
+# (.private_segment_fixed_size) values. Lines are counted, not read.
+kstats() {
+    awk '
+        function flush() {
+            if (name != "")
+                print name, n[name] + 0, v["vgpr_count"], v["sgpr_count"], v["vgpr_spill_count"],
+                      v["sgpr_spill_count"], v["group_segment_fixed_size"], v["private_segment_fixed_size"]
+            name = ""; split("", v)
+        }
+        /^[A-Za-z_][A-Za-z0-9_$.]*:/ { cur = $1; sub(/:.*/, "", cur) }
+        /^\.Lfunc_end/ { cur = "" }
+        cur != "" && /^\t[a-z]/ { n[cur]++ }
+        /^  - \./ { flush() }
+        /^ +(- )?\.name: / && !/^ {5}/ { name = $NF }
+        /^ +(- )?\.[a-z_]+: +[0-9]+$/ && !/^ {5}/ { k = $(NF - 1); sub(/^\./, "", k); sub(/:$/, "", k); v[k] = $NF }
+        END { flush() }' "$1" | sort
+}
 rc=0
 for n in $(units "$ROOT" | cut -d' ' -f1); do
     if [ ! -f "$TMP/a/$n.s" ] || [ ! -f "$TMP/b/$n.s" ]; then rc=1; echo "$n: not compiled on both sides"; continue; fi
     if d=$(diff <(norm "$TMP/a/$n.s") <(norm "$TMP/b/$n.s")); then echo "$n: identical"
-    else rc=1; echo "$n: DIFFERS ($(wc -l <<<"$d") diff lines)"; head -n 12 <<<"$d"; fi
+    else
+        rc=1; echo "$n: DIFFERS ($(wc -l <<<"$d") diff lines)"; head -n 12 <<<"$d"
+        echo "  per kernel, REV -> working tree: insts vgpr sgpr vgpr_spill sgpr_spill lds scratch"
+        join -a 1 -a 2 -e - -o 0,1.2,2.2,1.3,2.3,1.4,2.4,1.5,2.5,1.6,2.6,1.7,2.7,1.8,2.8 \
+            <(kstats "$TMP/a/$n.s") <(kstats "$TMP/b/$n.s") |
+            awk '{ printf "  %s:", $1; for (i = 2; i < NF; i += 2) printf " %s->%s", $i, $(i + 1); print "" }' |
+            { if command -v c++filt >/dev/null; then c++filt; else cat; fi; }
+    fi
 done
 exit $rc

@@ -63,6 +63,31 @@ def test_wide_forward_bit_exact(cuda, path, P, m, n, B, K, prob, per_sample, var
     assert np.array_equal(U.cpu().numpy(), Uo)
 
 
+@pytest.mark.parametrize("variant,H", [(0, 48), (1, 1)])    # unfolded 'diff', GNN clamps 'same'
+def test_stepwise_visit_lists_past_the_lds_budget(cuda, variant, H):
+    """The stepwise update keeps a sample's visit lists in LDS up to 4096 entries per wave
+    (csrc/dadmm_internal.h sw_vcap) and walks longer ones from global memory. A complete graph on
+    48 agents has 1128 edges = 4512 entries: that branch, over a full 64-column chunk and one with
+    four live lanes (n = 68)."""
+    from dadmm_hip import PreparedOperator, forward_raw, ingest
+    P, m, n, B, K = 48, 8, 68, 3, 3
+    A, b, _ = O.make_problem(P, m, n, B, seed=P + n)
+    graphs = [O.er_graph(P, 1.0, seed=3500)] * B
+    y0, U0, d0 = _inits(B, P, n, seed=K)
+    rng = np.random.default_rng(P * K)
+    hyp = O.hyp_table((0.5 * rng.standard_normal((K, H, 4))).astype(np.float32), MAXP)
+    g = ingest(graphs, P, B, cuda)
+    assert int(g.vptr[-1]) > 4096, "the lists fit the LDS budget: the global-list branch is not reached"
+    op = PreparedOperator(_t(A, cuda))
+    Y, U, st = forward_raw(op, _t(b, cuda), g, _t(hyp, cuda), _t(y0, cuda), _t(U0, cuda),
+                           _t(d0, cuda), variant=variant, want_U=True, path="stepwise")
+    torch.cuda.synchronize()
+    Yo, Uo, sto = O.forward_f32(A, b, graphs, hyp, y0, U0, d0, variant=variant)
+    assert int(st.item()) == sto == 0
+    assert np.array_equal(Y.cpu().numpy(), Yo), f"max |diff| {np.abs(Y.cpu().numpy() - Yo).max()}"
+    assert np.array_equal(U.cpu().numpy(), Uo)
+
+
 def test_wide_guard_fired_exact(cuda):
     """A NaN in b at P = 80: the batch-global gradient guard (unfolded_DLASSO.py:84-86) fires and
     the gated stepwise recomputation reproduces the reference's reset exactly."""
