@@ -827,18 +827,45 @@ int dadmm_loss_grad(int32_t K, int32_t B, int32_t P, int32_t n, int32_t n_store,
     return hip_rc(dadmm::launch_loss_grad(a, gout, dY, (hipStream_t)stream), "loss grad launch");
 }
 
+// The shape conditions of the hypernetwork GEMMs and their GCN epilogues, shared by the entry
+// points and the dadmm_hyper_form query.
+static int hyper_dims_check(int32_t rows, int32_t K, int32_t N, int32_t K1) {
+    if (rows < 0 || K < 1 || N < 1 || K1 < 1 || K1 > K)
+        return fail(DADMM_EINVAL, "bad linear dims rows=%d K=%d N=%d K1=%d", rows, K, N, K1);
+    return DADMM_OK;
+}
+static int hyper_split_check(int32_t K, int32_t K1) {
+    if (K1 < K && (K1 & 15))
+        return fail(DADMM_EUNSUPPORTED, "a split input needs K1 %% 16 == 0 (K1=%d)", K1);
+    return DADMM_OK;
+}
+// the GCN epilogue's row tile holds whole samples: at most 160 rows
+static int gcn_dims_check(int32_t B, int32_t P) {
+    if (B < 0 || P < 1 || P > 160) return fail(DADMM_EINVAL, "bad gcn dims B=%d P=%d (P <= 160)", B, P);
+    return DADMM_OK;
+}
+static int gcn_train_dims_check(int32_t B, int32_t P) {
+    if (B < 0 || P < 2 || P > dadmm::HYPER_GCN_TRAIN_MAX_P)
+        return fail(DADMM_EINVAL, "bad gcn dims B=%d P=%d (training BatchNorm needs P >= 2; P <= %d: the "
+                    "training tile of one sample must fit the LDS)", B, P, dadmm::HYPER_GCN_TRAIN_MAX_P);
+    return DADMM_OK;
+}
+static int gcn_bwd_dims_check(int32_t B, int32_t P, int32_t N) {
+    if (B < 0 || P < 2 || P > 64 || N < 1) return fail(DADMM_EINVAL, "bad gcn dims B=%d P=%d N=%d", B, P, N);
+    return DADMM_OK;
+}
+
 static int hyper_input(int32_t rows, int32_t K, int32_t N, const float* x1, int32_t ld1, int32_t K1,
                        const float* x2, int32_t ld2, const float* W, const float* y, int32_t ldy,
                        dadmm::HyperArgs* a) {
-    if (rows < 0 || K < 1 || N < 1 || K1 < 1 || K1 > K)
-        return fail(DADMM_EINVAL, "bad linear dims rows=%d K=%d N=%d K1=%d", rows, K, N, K1);
+    int rc = hyper_dims_check(rows, K, N, K1);
+    if (rc) return rc;
     if (!x1 || !W || !y || (K1 < K && !x2)) return fail(DADMM_EINVAL, "a required pointer is NULL");
     if ((K & 3) || (K1 & 3) || (ld1 & 3) || (K1 < K && (ld2 & 3)) || ld1 < K1 ||
         (K1 < K && ld2 < K - K1) || ldy < N)
         return fail(DADMM_EUNSUPPORTED, "K, K1 and the input row strides must be multiples of 4 "
                     "(K=%d K1=%d ld1=%d ld2=%d, ldy=%d >= N=%d)", K, K1, ld1, ld2, ldy, N);
-    if (K1 < K && (K1 & 15))
-        return fail(DADMM_EUNSUPPORTED, "a split input needs K1 %% 16 == 0 (K1=%d)", K1);
+    if ((rc = hyper_split_check(K, K1)) != DADMM_OK) return rc;
     if (!aligned16(x1) || (x2 && !aligned16(x2)) || !aligned16(W))
         return fail(DADMM_EINVAL, "x1, x2 and W must be 16-byte aligned");
     if ((int64_t)rows * (ld1 > ld2 ? ld1 : ld2) >= ((int64_t)1 << 31) ||
@@ -910,10 +937,10 @@ int dadmm_hyper_gcn(int32_t B, int32_t P, int32_t K, int32_t N, const float* x1,
                     const float* ahat, int32_t ahat_per_sample, const float* bn_mean,
                     const float* bn_var, const float* bn_weight, const float* bn_bias, float bn_eps,
                     float slope, float* y, int32_t ldy, void* stream) {
-    // the GCN epilogue's row tile holds whole samples: at most 160 rows
-    if (B < 0 || P < 1 || P > 160) return fail(DADMM_EINVAL, "bad gcn dims B=%d P=%d (P <= 160)", B, P);
+    int rc = gcn_dims_check(B, P);
+    if (rc) return rc;
     dadmm::HyperArgs a;
-    int rc = hyper_input(B * P, K, N, x1, ld1, K1, x2, ld2, W, y, ldy, &a);
+    rc = hyper_input(B * P, K, N, x1, ld1, K1, x2, ld2, W, y, ldy, &a);
     if (rc) return rc;
     if (!bias || !ahat || !bn_mean || !bn_var || !bn_weight || !bn_bias)
         return fail(DADMM_EINVAL, "a required pointer is NULL");
@@ -937,9 +964,10 @@ int dadmm_hyper_gcn_ex(int32_t B, int32_t P, int32_t K, int32_t N, const float* 
                        const float* ahat, int32_t ahat_per_sample, const float* bn_mean,
                        const float* bn_var, const float* bn_weight, const float* bn_bias, float bn_eps,
                        float slope, int32_t raw, float* y, int32_t ldy, void* stream) {
-    if (B < 0 || P < 1 || P > 160) return fail(DADMM_EINVAL, "bad gcn dims B=%d P=%d (P <= 160)", B, P);
+    int rc = gcn_dims_check(B, P);
+    if (rc) return rc;
     dadmm::HyperArgs a;
-    int rc = hyper_input(B * P, K, N, x, ldx, K, nullptr, 0, W, y, ldy, &a);
+    rc = hyper_input(B * P, K, N, x, ldx, K, nullptr, 0, W, y, ldy, &a);
     if (rc) return rc;
     if (ldw < K || (ldw & 3)) return fail(DADMM_EUNSUPPORTED, "ldw=%d must be >= K=%d and a multiple of 4", ldw, K);
     if (!ahat || (!raw && (!bias || !bn_mean || !bn_var || !bn_weight || !bn_bias)))
@@ -1072,11 +1100,11 @@ int dadmm::gcn_train_impl(int32_t B, int32_t P, int32_t K, int32_t N, const floa
                           void* stream) {
     if ((bn_running_mean == nullptr) != (bn_running_var == nullptr))
         return fail(DADMM_EINVAL, "running mean and variance: both or neither");
-    if (B < 0 || P < 2 || P > 160)
-        return fail(DADMM_EINVAL, "bad gcn dims B=%d P=%d (training BatchNorm needs P >= 2; P <= 160)", B, P);
+    int rc = gcn_train_dims_check(B, P);
+    if (rc) return rc;
     if (!(drop_p >= 0.0f && drop_p < 1.0f)) return fail(DADMM_EINVAL, "dropout p=%g not in [0, 1)", drop_p);
     dadmm::HyperArgs a;
-    int rc = hyper_input(B * P, K, N, x1, ld1, K1, x2, ld2, W, y, ldy, &a);
+    rc = hyper_input(B * P, K, N, x1, ld1, K1, x2, ld2, W, y, ldy, &a);
     if (rc) return rc;
     if (!bias || !ahat || !bn_weight || !bn_bias || !m_out || !mean_out || !var_out)
         return fail(DADMM_EINVAL, "a required pointer is NULL");
@@ -1171,7 +1199,8 @@ int dadmm_hyper_gcn_train_bwd(int32_t B, int32_t P, int32_t N, const float* dy, 
                               float bn_eps, const float* ahat, int32_t ahat_per_sample, float slope,
                               float drop_p, uint64_t seed, int32_t site, float* dz, float* part,
                               int32_t bn_eval, void* stream) {
-    if (B < 0 || P < 2 || P > 64 || N < 1) return fail(DADMM_EINVAL, "bad gcn dims B=%d P=%d N=%d", B, P, N);
+    int rc = gcn_bwd_dims_check(B, P, N);
+    if (rc) return rc;
     if (!dy || !m || !mean || !var || !bn_weight || !ahat || !dz || !part)
         return fail(DADMM_EINVAL, "a required pointer is NULL");
     if ((int64_t)B * P * N >= ((int64_t)1 << 31)) return fail(DADMM_EUNSUPPORTED, "operand larger than 2^31 floats");
@@ -1180,14 +1209,17 @@ int dadmm_hyper_gcn_train_bwd(int32_t B, int32_t P, int32_t N, const float* dy, 
     return hip_rc(dadmm::launch_gcn_bwd(a, (hipStream_t)stream), "gcn backward launch");
 }
 
-int dadmm_hyper_linear_gcn_bwd(int32_t B, int32_t P, int32_t K, int32_t N, const float* x, int32_t ldx,
-                               const float* W, const float* m, const float* mean, const float* var,
-                               const float* bn_weight, float bn_eps, const float* ahat, int32_t ahat_per_sample,
-                               float slope, float drop_p, uint64_t seed, int32_t site, float* dz, float* part,
-                               int32_t bn_eval, void* stream) {
-    if (B < 0 || P < 2 || P > 64 || N < 1) return fail(DADMM_EINVAL, "bad gcn dims B=%d P=%d N=%d", B, P, N);
+// kwave: 0 = the GEMM of dadmm_hyper_linear (never splits K); P = the GCN-class GEMM of
+// hyper_linear_gcn_dx (may split K over two wave sets on small grids)
+static int linear_gcn_bwd_kw(int32_t kwave, int32_t B, int32_t P, int32_t K, int32_t N, const float* x, int32_t ldx,
+                             const float* W, const float* m, const float* mean, const float* var,
+                             const float* bn_weight, float bn_eps, const float* ahat, int32_t ahat_per_sample,
+                             float slope, float drop_p, uint64_t seed, int32_t site, float* dz, float* part,
+                             int32_t bn_eval, void* stream) {
+    int rc = gcn_bwd_dims_check(B, P, N);
+    if (rc) return rc;
     dadmm::HyperArgs a;
-    int rc = hyper_input(B * P, K, N, x, ldx, K, nullptr, 0, W, dz, N, &a);
+    rc = hyper_input(B * P, K, N, x, ldx, K, nullptr, 0, W, dz, N, &a);
     if (rc) return rc;
     if (!m || !mean || !var || !bn_weight || !ahat || !part) return fail(DADMM_EINVAL, "a required pointer is NULL");
     if ((N & 3) || !aligned16(dz)) return fail(DADMM_EUNSUPPORTED, "N %% 4 == 0 and a 16-byte aligned dz required");
@@ -1196,7 +1228,7 @@ int dadmm_hyper_linear_gcn_bwd(int32_t B, int32_t P, int32_t K, int32_t N, const
         return fail(DADMM_EUNSUPPORTED, "operand larger than 2^31 floats");
     a.B = B;
     a.P = P;
-    a.kwave = P;   // GCN-class GEMM (the K split may apply, hyper_kwave)
+    a.kwave = kwave;
     a.splits = 1;
     a.ahat = ahat;
     a.ahat_per_sample = ahat_per_sample ? 1 : 0;
@@ -1212,6 +1244,91 @@ int dadmm_hyper_linear_gcn_bwd(int32_t B, int32_t P, int32_t K, int32_t N, const
     a.part = part;
     a.bn_eval = bn_eval ? 1 : 0;
     return hip_rc(dadmm::launch_hyper(a, HYPER_EPI_GCN_BWD, (hipStream_t)stream), "linear + gcn backward launch");
+}
+
+// The C ABI's fused launch keeps its header's promise, the bits of dadmm_hyper_linear followed by
+// dadmm_hyper_gcn_train_bwd: its GEMM is dadmm_hyper_linear's, which never splits K.
+int dadmm_hyper_linear_gcn_bwd(int32_t B, int32_t P, int32_t K, int32_t N, const float* x, int32_t ldx,
+                               const float* W, const float* m, const float* mean, const float* var,
+                               const float* bn_weight, float bn_eps, const float* ahat, int32_t ahat_per_sample,
+                               float slope, float drop_p, uint64_t seed, int32_t site, float* dz, float* part,
+                               int32_t bn_eval, void* stream) {
+    return linear_gcn_bwd_kw(0, B, P, K, N, x, ldx, W, m, mean, var, bn_weight, bn_eps, ahat, ahat_per_sample, slope,
+                             drop_p, seed, site, dz, part, bn_eval, stream);
+}
+
+extern "C++" {
+namespace dadmm {
+// The training backward's fused launch: the GCN-class GEMM (the bits of hyper_linear_gcn_dx followed
+// by dadmm_hyper_gcn_train_bwd, whichever of the two the backward takes for a layer).
+int hyper_linear_gcn_bwd(int32_t B, int32_t P, int32_t K, int32_t N, const float* x, int32_t ldx, const float* W,
+                         const float* m, const float* mean, const float* var, const float* bn_weight, float bn_eps,
+                         const float* ahat, int32_t ahat_per_sample, float slope, float drop_p, uint64_t seed,
+                         int32_t site, float* dz, float* part, int32_t bn_eval, void* stream) {
+    return linear_gcn_bwd_kw(P, B, P, K, N, x, ldx, W, m, mean, var, bn_weight, bn_eps, ahat, ahat_per_sample, slope,
+                             drop_p, seed, site, dz, part, bn_eval, stream);
+}
+}  // namespace dadmm
+}
+
+static_assert(DADMM_HYPER_FORM_LINEAR == HYPER_EPI_BIAS && DADMM_HYPER_FORM_GCN == HYPER_EPI_GCN &&
+              DADMM_HYPER_FORM_HEAD == HYPER_EPI_HEAD && DADMM_HYPER_FORM_GCN_TRAIN == HYPER_EPI_GCN_TRAIN &&
+              DADMM_HYPER_FORM_LINEAR_GCN_BWD == HYPER_EPI_GCN_BWD, "the query's kinds are the epilogue codes");
+
+int dadmm_hyper_form(int32_t kind, int32_t B, int32_t P, int32_t K, int32_t N, int32_t K1,
+                     dadmm_hyper_form_t* form) {
+    if (form == nullptr) return fail(DADMM_EINVAL, "form is NULL");
+    *form = dadmm_hyper_form_t{};
+    if (kind < DADMM_HYPER_FORM_LINEAR || kind > DADMM_HYPER_FORM_GCN_BWD)
+        return fail(DADMM_EINVAL, "unknown hypernetwork launch kind %d", kind);
+    int rc = DADMM_OK;
+    if (kind == DADMM_HYPER_FORM_GCN_BWD) {   // no GEMM: K and K1 unused
+        if ((rc = gcn_bwd_dims_check(B, P, N)) != DADMM_OK) return rc;
+        dadmm::GcnBwdArgs g{};
+        g.B = B;
+        g.P = P;
+        g.N = N;
+        const dadmm::GcnBwdForm f = dadmm::plan_gcn_bwd(g);
+        form->nt = f.nt;
+        form->pr = f.pr;
+        form->grid = f.grid;
+        return ok();
+    }
+    const bool gcn = kind != DADMM_HYPER_FORM_LINEAR && kind != DADMM_HYPER_FORM_HEAD;
+    if (kind == DADMM_HYPER_FORM_GCN) rc = gcn_dims_check(B, P);
+    if (kind == DADMM_HYPER_FORM_GCN_TRAIN) rc = gcn_train_dims_check(B, P);
+    if (kind == DADMM_HYPER_FORM_LINEAR_GCN_BWD) rc = gcn_bwd_dims_check(B, P, N);
+    if (rc) return rc;
+    if (!gcn) P = 1;
+    if (gcn && (int64_t)B * P >= ((int64_t)1 << 31)) return fail(DADMM_EUNSUPPORTED, "operand larger than 2^31 floats");
+    if ((rc = hyper_dims_check(B * P, K, N, K1)) != DADMM_OK) return rc;
+    if ((K & 3) || (K1 & 3)) return fail(DADMM_EUNSUPPORTED, "K and K1 must be multiples of 4 (K=%d K1=%d)", K, K1);
+    if ((rc = hyper_split_check(K, K1)) != DADMM_OK) return rc;
+    if (kind != DADMM_HYPER_FORM_LINEAR && kind != DADMM_HYPER_FORM_GCN && kind != DADMM_HYPER_FORM_GCN_TRAIN && K1 != K)
+        return fail(DADMM_EINVAL, "this launch takes one input: K1=%d != K=%d", K1, K);
+    if (kind != DADMM_HYPER_FORM_LINEAR && kind != DADMM_HYPER_FORM_GCN && (N & 3))
+        return fail(DADMM_EUNSUPPORTED, "N %% 4 == 0 required (N=%d)", N);
+    dadmm::HyperArgs a{};
+    a.rows = B * P;
+    a.B = B;
+    a.P = P;
+    a.K = K;
+    a.K1 = K1;
+    a.N = N;
+    // as the entry points set it: the GCN layers' GEMMs may take the K split, the C ABI's fused
+    // backward runs dadmm_hyper_linear's GEMM
+    a.kwave = (gcn && kind != DADMM_HYPER_FORM_LINEAR_GCN_BWD) ? P : 0;
+    a.splits = (kind == DADMM_HYPER_FORM_LINEAR || kind == DADMM_HYPER_FORM_LINEAR_GCN_BWD) ? 1 : 0;
+    dadmm::HyperForm f;
+    if ((rc = hip_rc(dadmm::plan_hyper(a, kind, f), "hypernetwork launch plan")) != DADMM_OK) return rc;
+    form->wr = f.wr;
+    form->dma = f.dma;
+    form->ks = f.ks;
+    form->split = f.split;
+    form->gcn32 = f.gcn32;
+    form->grid = f.grid;
+    form->samples_per_tile = (gcn && f.grid > 0) ? a.S_t : 0;
+    return DADMM_OK;
 }
 
 int dadmm_hyper_linear_ln_train(int32_t rows, int32_t K, int32_t N, const float* x, int32_t ldx,

@@ -930,18 +930,33 @@ __global__ __launch_bounds__(THREADS) void rownorm_kernel(RowNormArgs a) {
     }
 }
 
-template <int WR, int EPI, bool SPLIT, bool DMA, int KS = 1>
-hipError_t launch_one(int grid, const HyperArgs& a, hipStream_t st) {
-    size_t lds = DMA ? 4 * (size_t)HYPER_DQ * (2 * WR + 4) * 256 : 0;   // the ring
-    if (EPI == HYPER_EPI_GCN || EPI == HYPER_EPI_GCN_TRAIN || EPI == HYPER_EPI_GCN_BWD) {   // the epilogue (reuses the ring)
-        size_t e = 4 * ((size_t)32 * WR * ZS + (((size_t)a.S_t * a.P * a.P + 3) & ~(size_t)3) + 4 * TN);
-        if (EPI == HYPER_EPI_GCN_TRAIN) e += 4 * ((size_t)32 * WR * ZS + 2 * (size_t)a.S_t * TN);
+// Dynamic LDS of linear_kernel<wr, epi, ., dma, .> for the tile plan in `a` (S_t, P): the ring, or
+// the GCN epilogue that reuses it. launch_one sizes the launch with it and plan_hyper refuses a
+// tile that does not fit (KS = 2 adds the static 8 KB x WR of the K-half sums).
+static size_t lds_bytes(int wr, int epi, bool dma, const HyperArgs& a) {
+    size_t lds = dma ? 4 * (size_t)HYPER_DQ * (2 * wr + 4) * 256 : 0;   // the ring
+    if (epi == HYPER_EPI_GCN || epi == HYPER_EPI_GCN_TRAIN || epi == HYPER_EPI_GCN_BWD) {   // the epilogue (reuses the ring)
+        size_t e = 4 * ((size_t)32 * wr * ZS + (((size_t)a.S_t * a.P * a.P + 3) & ~(size_t)3) + 4 * TN);
+        if (epi == HYPER_EPI_GCN_TRAIN) e += 4 * ((size_t)32 * wr * ZS + 2 * (size_t)a.S_t * TN);
         lds = e > lds ? e : lds;
         // the prefetched M tile and statistics, past both the ring and the epilogue tile
-        if (EPI == HYPER_EPI_GCN_BWD) lds += 4 * ((size_t)32 * WR * TN + 2 * (size_t)((a.S_t + 3) & ~3) * TN);
+        if (epi == HYPER_EPI_GCN_BWD) lds += 4 * ((size_t)32 * wr * TN + 2 * (size_t)((a.S_t + 3) & ~3) * TN);
     }
-    // (KS = 2: plus the static 8 KB x WR of the K-half sums)
-    if (lds + (KS == 2 ? (size_t)8192 * WR : 0) > 160 * 1024) return hipErrorInvalidConfiguration;
+    return lds;
+}
+constexpr size_t LDS_MAX = 160 * 1024;
+// the largest sample the training epilogue's 160-row tile holds (S_t = 1; HYPER_GCN_TRAIN_MAX_P)
+constexpr size_t train_lds_1(size_t P) { return 4 * (2 * 160 * (size_t)ZS + ((P * P + 3) & ~(size_t)3) + 4 * TN + 2 * TN); }
+static_assert(train_lds_1(HYPER_GCN_TRAIN_MAX_P) <= LDS_MAX && train_lds_1(HYPER_GCN_TRAIN_MAX_P + 1) > LDS_MAX,
+              "HYPER_GCN_TRAIN_MAX_P is the largest P whose training tile fits the LDS");
+static bool lds_fits(int wr, int ks, int epi, bool dma, const HyperArgs& a) {
+    return lds_bytes(wr, epi, dma, a) + (ks == 2 ? (size_t)8192 * wr : 0) <= LDS_MAX;
+}
+
+template <int WR, int EPI, bool SPLIT, bool DMA, int KS = 1>
+hipError_t launch_one(int grid, const HyperArgs& a, hipStream_t st) {
+    const size_t lds = lds_bytes(WR, EPI, DMA, a);
+    if (!lds_fits(WR, KS, EPI, DMA, a)) return hipErrorInvalidConfiguration;
     if (lds > 64 * 1024 - (KS == 2 ? (size_t)8192 * WR : 0)) {
         hipError_t e = hipFuncSetAttribute((const void*)linear_kernel<WR, EPI, SPLIT, DMA, KS>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -976,8 +991,7 @@ static bool use_dma(int K, int splits) {
 }
 
 template <int EPI>
-hipError_t launch_epi(int wr, int ks, int grid, const HyperArgs& a, hipStream_t st) {
-    const bool dma = use_dma(a.K, a.splits);
+hipError_t launch_epi(int wr, bool dma, int ks, int grid, const HyperArgs& a, hipStream_t st) {
     if (a.K1 < a.K) return launch_wr<EPI, true>(wr, dma, ks, grid, a, st);
     return launch_wr<EPI, false>(wr, dma, ks, grid, a, st);
 }
@@ -1023,6 +1037,11 @@ static int pick_tiles(HyperArgs& a, int epi) {
         a.gm = (units + su - 1) / su;
         if ((long)a.gm * a.gn >= 480) break;   // ~2 workgroups per CU: balance + latency hiding
     }
+    if (wr == 0 && gcn && unit <= 160) {   // a sample of 129..160 nodes: only the 160-row tile holds it
+        wr = 5;
+        a.S_t = 1;
+        a.gm = units;
+    }
     return wr;
 }
 
@@ -1052,7 +1071,7 @@ static int pick_split_tiles(HyperArgs& a, int K, int& splits) {
 // the 32x32x2 GCN kernel (gcn32_kernel) for inference GCN layers on an unsplit input whose grid
 // of 256-row tiles still covers the CUs; DADMM_GCN32=0 in the environment selects linear_kernel
 // (A/B timing)
-static bool try_gcn32(HyperArgs& a, hipStream_t st, hipError_t& err) {
+static bool plan_gcn32(HyperArgs& a) {
     static int enabled = -1;
     if (enabled < 0) {
         const char* e = getenv("DADMM_GCN32");
@@ -1064,17 +1083,18 @@ static bool try_gcn32(HyperArgs& a, hipStream_t st, hipError_t& err) {
     const int S_t = hyper::G32_TM / a.P;
     const long gm = (a.B + S_t - 1) / S_t, gn = (a.N + hyper::TN - 1) / hyper::TN;
     if (gm * gn < 256) return false;
-    const size_t lds = hyper::g32_lds_bytes(S_t, a.P);
-    if (lds > 160 * 1024) return false;
+    if (hyper::g32_lds_bytes(S_t, a.P) > hyper::LDS_MAX) return false;
     a.S_t = S_t;
     a.gm = (int)gm;
     a.gn = (int)gn;
-    err = hipFuncSetAttribute((const void*)hyper::gcn32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (err == hipSuccess) {
-        hipLaunchKernelGGL(hyper::gcn32_kernel, dim3((unsigned)(gm * gn)), dim3(64 * hyper::G32_WAVES), lds, st, a);
-        err = hipGetLastError();
-    }
     return true;
+}
+static hipError_t launch_gcn32(const HyperArgs& a, int grid, hipStream_t st) {
+    const size_t lds = hyper::g32_lds_bytes(a.S_t, a.P);
+    hipError_t err = hipFuncSetAttribute((const void*)hyper::gcn32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL(hyper::gcn32_kernel, dim3((unsigned)grid), dim3(64 * hyper::G32_WAVES), lds, st, a);
+    return hipGetLastError();
 }
 
 // The K split over two wave sets of a workgroup (linear_kernel KS = 2): where the grid of 32-row
@@ -1101,13 +1121,22 @@ static bool hyper_kwave(const HyperArgs& a, int epi, int rows) {
     return tiles < 480;
 }
 
-hipError_t launch_hyper(HyperArgs a, int epi, hipStream_t st) {
+// Everything launch_hyper decides from the shape, and nothing launched: the tile plan goes into
+// `a` (S_t, gm, gn, splits), the kernel form into `f`. The dadmm_hyper_form query asks here too.
+// f.grid == 0: nothing to launch.
+hipError_t plan_hyper(HyperArgs& a, int epi, HyperForm& f) {
+    f = HyperForm{};
     const bool gcn = epi == HYPER_EPI_GCN || epi == HYPER_EPI_GCN_TRAIN || epi == HYPER_EPI_GCN_BWD;
     const int units = gcn ? a.B : a.rows;
     if (units <= 0 || a.N <= 0) return hipSuccess;
+    if (epi < HYPER_EPI_BIAS || epi > HYPER_EPI_GCN_BWD) return hipErrorInvalidValue;
     if (a.K1 < a.K && (a.K1 & 15)) return hipErrorInvalidValue;
-    hipError_t gerr = hipSuccess;
-    if (epi == HYPER_EPI_GCN && try_gcn32(a, st, gerr)) return gerr;
+    f.split = a.K1 < a.K;
+    if (epi == HYPER_EPI_GCN && plan_gcn32(a)) {
+        f.gcn32 = 1;
+        f.grid = a.gm * a.gn;
+        return hipSuccess;
+    }
     int wr = 0, ks = 1;
     if (hyper_kwave(a, epi, gcn ? a.B * a.P : a.rows)) {   // 32-row tiles (whole samples), K split in two
         ks = 2;
@@ -1123,14 +1152,28 @@ hipError_t launch_hyper(HyperArgs a, int epi, hipStream_t st) {
         wr = pick_tiles(a, epi);
     }
     if (wr == 0) return hipErrorInvalidValue;
+    if (wr == 5 && !gcn) return hipErrorInvalidValue;
     if (a.splits < 1) a.splits = 1;
-    const int grid = a.gm * a.gn * a.splits;
+    f.wr = wr;
+    f.ks = ks;
+    f.dma = wr != 1 && hyper::use_dma(a.K, a.splits);   // the 32-row tiles run on the register ring
+    if (!hyper::lds_fits(wr, ks, epi, f.dma != 0, a)) return hipErrorInvalidConfiguration;
+    f.grid = a.gm * a.gn * a.splits;
+    return hipSuccess;
+}
+
+hipError_t launch_hyper(HyperArgs a, int epi, hipStream_t st) {
+    HyperForm f;
+    const hipError_t e = plan_hyper(a, epi, f);
+    if (e != hipSuccess || f.grid == 0) return e;
+    if (f.gcn32) return launch_gcn32(a, f.grid, st);
+    const bool dma = f.dma != 0;
     switch (epi) {
-        case HYPER_EPI_BIAS: return hyper::launch_epi<HYPER_EPI_BIAS>(wr, ks, grid, a, st);
-        case HYPER_EPI_GCN: return hyper::launch_epi<HYPER_EPI_GCN>(wr, ks, grid, a, st);
-        case HYPER_EPI_HEAD: return hyper::launch_epi<HYPER_EPI_HEAD>(wr, ks, grid, a, st);
-        case HYPER_EPI_GCN_TRAIN: return hyper::launch_epi<HYPER_EPI_GCN_TRAIN>(wr, ks, grid, a, st);
-        case HYPER_EPI_GCN_BWD: return hyper::launch_epi<HYPER_EPI_GCN_BWD>(wr, ks, grid, a, st);
+        case HYPER_EPI_BIAS: return hyper::launch_epi<HYPER_EPI_BIAS>(f.wr, dma, f.ks, f.grid, a, st);
+        case HYPER_EPI_GCN: return hyper::launch_epi<HYPER_EPI_GCN>(f.wr, dma, f.ks, f.grid, a, st);
+        case HYPER_EPI_HEAD: return hyper::launch_epi<HYPER_EPI_HEAD>(f.wr, dma, f.ks, f.grid, a, st);
+        case HYPER_EPI_GCN_TRAIN: return hyper::launch_epi<HYPER_EPI_GCN_TRAIN>(f.wr, dma, f.ks, f.grid, a, st);
+        case HYPER_EPI_GCN_BWD: return hyper::launch_epi<HYPER_EPI_GCN_BWD>(f.wr, dma, f.ks, f.grid, a, st);
         default: return hipErrorInvalidValue;
     }
 }

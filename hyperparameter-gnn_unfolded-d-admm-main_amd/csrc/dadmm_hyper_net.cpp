@@ -369,7 +369,7 @@ static int train_backward(const dadmm_hyper_net* net, int32_t B, const float* At
     // GCN layers, last to first: dZ (gcn backward), [dgamma, dbeta, dbias], dW, dX. Layer 5's
     // gcn backward is its own launch (its dy comes from the LayerNorm backward); layers 4 .. 1 run
     // theirs in the epilogue of the input-gradient GEMM of the layer above
-    // (dadmm_hyper_linear_gcn_bwd: no dy round trip, one launch instead of two)
+    // (hyper_linear_gcn_bwd: no dy round trip, one launch instead of two)
     float* dZ = nullptr;   // this layer's dZ once formed
     for (int i = 4; i >= 0; --i) {
         const int N = net->width[i];
@@ -389,10 +389,10 @@ static int train_backward(const dadmm_hyper_net* net, int32_t B, const float* At
             if (gcn_bwd_fused(B, P, Kin)) {
                 // layer i - 1's dZ straight from this layer's dZ (not the buffer holding it)
                 float* nz = defer ? d.dZ[i - 1] : (dZ == w.dx[0] ? w.dx[1] : w.dx[0]);
-                TRY(dadmm_hyper_linear_gcn_bwd(B, P, N, Kin, dZ, N, g->conv_wt[i], sv->m[i - 1], sv->mean[i - 1],
-                                               sv->var[i - 1], net->bn_w[i - 1], net->bn_eps[i - 1], ahat,
-                                               ahat_per_sample, LEAKY, net->drop_enc, seed, i - 1, nz,
-                                               defer ? d.pgcn[i - 1] : w.part, net->bn_eval, stream));
+                TRY(dadmm::hyper_linear_gcn_bwd(B, P, N, Kin, dZ, N, g->conv_wt[i], sv->m[i - 1], sv->mean[i - 1],
+                                                sv->var[i - 1], net->bn_w[i - 1], net->bn_eps[i - 1], ahat,
+                                                ahat_per_sample, LEAKY, net->drop_enc, seed, i - 1, nz,
+                                                defer ? d.pgcn[i - 1] : w.part, net->bn_eval, stream));
                 dZ = nz;
             } else {
                 // dX into the buffer dx held (gcn backward consumed it)

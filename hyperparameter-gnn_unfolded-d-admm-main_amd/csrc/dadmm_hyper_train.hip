@@ -436,17 +436,23 @@ static hipError_t launch_gcn_bwd_nt(const GcnBwdArgs& a, int grid, size_t lds, h
     return hipGetLastError();
 }
 
+GcnBwdForm plan_gcn_bwd(const GcnBwdArgs& a) {
+    GcnBwdForm f{};
+    if (a.B <= 0 || a.N <= 0) return f;
+    f.lds = 4 * ((size_t)a.P * hyper_train::CB + (size_t)a.P * a.P);
+    f.grid = a.B * ((a.N + hyper_train::CB - 1) / hyper_train::CB);
+    f.nt = f.grid >= hyper_train::GCNBWD_WIDE_MIN ? 64 : hyper_train::THREADS;
+    f.pr = a.P <= hyper_train::GCNBWD_PR ? hyper_train::GCNBWD_PR : 0;
+    return f;
+}
+
 hipError_t launch_gcn_bwd(const GcnBwdArgs& a, hipStream_t st) {
-    if (a.B <= 0 || a.N <= 0) return hipSuccess;
-    const size_t lds = 4 * ((size_t)a.P * hyper_train::CB + (size_t)a.P * a.P);
-    const int ncb = (a.N + hyper_train::CB - 1) / hyper_train::CB;
-    const int grid = a.B * ncb;
-    constexpr int T4 = hyper_train::THREADS;
-    if (a.P <= hyper_train::GCNBWD_PR)
-        return grid >= hyper_train::GCNBWD_WIDE_MIN ? launch_gcn_bwd_nt<64, hyper_train::GCNBWD_PR>(a, grid, lds, st)
-                                             : launch_gcn_bwd_nt<T4, hyper_train::GCNBWD_PR>(a, grid, lds, st);
-    return grid >= hyper_train::GCNBWD_WIDE_MIN ? launch_gcn_bwd_nt<64, 0>(a, grid, lds, st)
-                                         : launch_gcn_bwd_nt<T4, 0>(a, grid, lds, st);
+    const GcnBwdForm f = plan_gcn_bwd(a);
+    if (f.grid == 0) return hipSuccess;
+    constexpr int T4 = hyper_train::THREADS, PR = hyper_train::GCNBWD_PR;
+    if (f.pr != 0)
+        return f.nt == 64 ? launch_gcn_bwd_nt<64, PR>(a, f.grid, f.lds, st) : launch_gcn_bwd_nt<T4, PR>(a, f.grid, f.lds, st);
+    return f.nt == 64 ? launch_gcn_bwd_nt<64, 0>(a, f.grid, f.lds, st) : launch_gcn_bwd_nt<T4, 0>(a, f.grid, f.lds, st);
 }
 
 hipError_t launch_rownorm_bwd(const RowNormBwdArgs& a, hipStream_t st) {

@@ -306,11 +306,27 @@ __host__ __device__ inline uint32_t drop_threshold(float p) {
     return t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
 }
 hipError_t launch_hyper(HyperArgs a, int epi, hipStream_t st);
+// The kernel form launch_hyper takes for a shape (plan_hyper: what the launch itself asks, nothing
+// launched): the row tile (32 wr rows), the LDS-DMA operand ring, the K split over two wave sets
+// (ks = 2), the split input (K1 < K), the 32x32 inference kernel, the grid (0: nothing to launch).
+struct HyperForm {
+    int wr, dma, ks, split, gcn32, grid;
+};
+hipError_t plan_hyper(HyperArgs& a, int epi, HyperForm& f);
+// dadmm_hyper_gcn_train: the 160-row tile's two [160][68] tiles, one sample's A_hat [P][P] and its
+// column tables fill the 160 KB LDS up to P = 137 (dadmm_hyper.hip asserts the arithmetic)
+constexpr int HYPER_GCN_TRAIN_MAX_P = 137;
 // dadmm_hyper_linear_ex (no bias) as a GCN-class GEMM: a GCN layer's input gradient dX = dZ W on
-// its B samples of P rows, which may take the K split like the fused dadmm_hyper_linear_gcn_bwd
+// its B samples of P rows, which may take the K split like the fused hyper_linear_gcn_bwd
 // of the same shape (same bits either way); the C-ABI's linears never split (the decoder's)
 int hyper_linear_gcn_dx(int32_t P, int32_t rows, int32_t K, int32_t N, const float* x, int32_t ldx, const float* W,
                         const float* addend, int32_t ld_add, float* y, int32_t ldy, void* stream);
+// dadmm_hyper_linear_gcn_bwd on that GCN-class GEMM: the training backward's fused launch, bit-identical to
+// hyper_linear_gcn_dx + dadmm_hyper_gcn_train_bwd (the C-ABI entry runs dadmm_hyper_linear's GEMM instead)
+int hyper_linear_gcn_bwd(int32_t B, int32_t P, int32_t K, int32_t N, const float* x, int32_t ldx, const float* W,
+                         const float* m, const float* mean, const float* var, const float* bn_weight, float bn_eps,
+                         const float* ahat, int32_t ahat_per_sample, float slope, float drop_p, uint64_t seed,
+                         int32_t site, float* dz, float* part, int32_t bn_eval, void* stream);
 int hyper_linear_splits(int rows, int K, int N);
 struct RowNormArgs {
     const float* x;         // [nsum][rows][C] (row stride C, partial q at x + q * sum_stride)
@@ -364,6 +380,13 @@ struct GcnBwdArgs {
     int bn_eval;            // BatchNorm on constant (running) statistics: no batch-statistics terms
 };
 hipError_t launch_gcn_bwd(const GcnBwdArgs& a, hipStream_t st);
+// The form launch_gcn_bwd takes (nothing launched): threads per workgroup (64 on grids that fill
+// the chip, else 256), rows held in registers (8 at P <= 8, else 0: the per-row loop), the grid
+struct GcnBwdForm {
+    int nt, pr, grid;
+    size_t lds;
+};
+GcnBwdForm plan_gcn_bwd(const GcnBwdArgs& a);
 // dadmm_hyper_gcn_train with a column slice of W (row stride ldw >= K) and an addend
 // [B*P][ld_add] (nullable) added to the mix A_hat (x W^T) before the bias (dadmm_abi.cpp)
 int gcn_train_impl(int32_t B, int32_t P, int32_t K, int32_t N, const float* x1, int32_t ld1, int32_t K1,

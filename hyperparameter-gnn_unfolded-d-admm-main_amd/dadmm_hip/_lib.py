@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # scripts/time_variants.sh); it is still the HIP library, there is no other path
 LIB_PATH = os.environ.get("DADMM_LIB_VARIANT") or os.path.join(_HERE, "libdadmm.so")
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 DADMM_OK, DADMM_EINVAL, DADMM_EUNSUPPORTED, DADMM_EHIP = 0, -1, -2, -3
 VARIANT_UNFOLDED, VARIANT_GNN = 0, 1
 STATUS_Y_NONFINITE, STATUS_U_NONFINITE, STATUS_GRAD_NAN, STATUS_YNEXT_NAN = 1, 2, 4, 8
@@ -68,6 +68,7 @@ EXPORTED_SYMBOLS = (
     "dadmm_hyper_train_wgrad_scratch_bytes",
     "dadmm_hyper_linear_gcn_bwd",
     "dadmm_hyper_head_train",
+    "dadmm_hyper_form",
     "dadmm_hyper_bn_running_scratch_bytes",
     "dadmm_hyper_bn_running_update",
     "dadmm_gnn_flag_bytes",
@@ -151,6 +152,20 @@ class HyperGrads(ctypes.Structure):
                 ("dec_w", ctypes.c_void_p * 3), ("dec_b", ctypes.c_void_p * 3), ("ln_wb", ctypes.c_void_p * 3),
                 ("fc_w", ctypes.c_void_p), ("fc_b", ctypes.c_void_p),
                 ("conv_wt", ctypes.c_void_p * 5), ("dec_wt", ctypes.c_void_p * 3), ("fc_wt", ctypes.c_void_p)]
+
+
+# dadmm_hyper_form's `kind` (DADMM_HYPER_FORM_* of include/dadmm.h)
+HYPER_FORM_KINDS = {"linear": 0, "gcn": 1, "head": 2, "gcn_train": 3, "linear_gcn_bwd": 4, "gcn_bwd": 5}
+
+
+class HyperForm(ctypes.Structure):
+    """dadmm_hyper_form_t: the kernel form a hypernetwork launch takes."""
+    _fields_ = [(f, ctypes.c_int32) for f in ("wr", "dma", "ks", "split", "gcn32", "nt", "pr", "grid",
+                                              "samples_per_tile")]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
 
 def load() -> ctypes.CDLL:
     """Load libdadmm.so once; raises if it is absent (no silent fallback)."""
@@ -290,6 +305,8 @@ def load() -> ctypes.CDLL:
     L.dadmm_hyper_linear_gcn_bwd.argtypes = [i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp, ctypes.c_float, vp,
                                              i32, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, i32, vp, vp,
                                              i32, vp]
+    L.dadmm_hyper_form.restype = ctypes.c_int
+    L.dadmm_hyper_form.argtypes = [i32] * 6 + [ctypes.POINTER(HyperForm)]
     L.dadmm_hyper_bn_running_scratch_bytes.restype = ctypes.c_size_t
     L.dadmm_hyper_bn_running_scratch_bytes.argtypes = [i32, vp, i32, i32]
     L.dadmm_hyper_bn_running_update.restype = ctypes.c_int

@@ -303,6 +303,21 @@ def tiled_form(dims_or_shape, record: bool = False) -> int:
     return int(_lib.load().dadmm_tiled_form(ctypes.byref(d), 1 if record else 0))
 
 
+def hyper_form(kind: str, B: int, P: int, K: int, N: int, K1=None):
+    """Which kernel form a hypernetwork launch takes (dadmm_hyper_form; no GPU needed, nothing
+    launched). kind: "linear", "gcn", "head", "gcn_train", "linear_gcn_bwd" (B samples of P nodes;
+    rows = B and P unused for "linear" / "head", where N = 4 H) or "gcn_bwd" (the stand-alone GCN
+    block backward: K unused). Returns a dict: wr (row tile / 32), dma (the LDS-DMA ring), ks (2: the
+    K loop split over two wave sets), split (K1 < K), gcn32 (the 32x32 inference kernel), nt / pr
+    ("gcn_bwd" only), grid, samples_per_tile; or the negative DADMM_E* code the launch would fail
+    with (``_lib.load().dadmm_last_error()`` has its text). It reads DADMM_GCN32 / DADMM_HYPER_KW as
+    the launch does."""
+    f = _lib.HyperForm()
+    rc = int(_lib.load().dadmm_hyper_form(_lib.HYPER_FORM_KINDS[kind], B, P, K, N, K if K1 is None else K1,
+                                          ctypes.byref(f)))
+    return rc if rc != _lib.DADMM_OK else f.as_dict()
+
+
 class Trajectory:
     """What the adjoint consumes: the n-padded iterates Y, pre-clamp gradients Grec and dual
     states Urec ([K,B,P,n_store] each), the inits y0 / d0 and the hyper-parameter table;

@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define DADMM_ABI_VERSION 20
+#define DADMM_ABI_VERSION 21
 
 enum {
     DADMM_OK = 0,
@@ -432,7 +432,8 @@ int dadmm_loss_grad(int32_t K, int32_t B, int32_t P, int32_t n, int32_t n_store,
  *
  * dadmm_hyper_gcn: GCNConv(K -> N) -> leaky_relu(slope) -> BatchNorm1d (eval) for B samples of P
  *   nodes (rows b*P + p): y = BN(leaky(A_hat[b] (x W^T) + bias)); ahat [B or 1][P][P] is
- *   D^-1/2 (Adj + I) D^-1/2 (ahat_per_sample = 0: one graph for every sample).
+ *   D^-1/2 (Adj + I) D^-1/2 (ahat_per_sample = 0: one graph for every sample). P <= 160: a row
+ *   tile holds whole samples (129..160 nodes: one sample per 160-row tile at every batch size).
  *   Replaces: GCNConv + F.leaky_relu + self.bn_i of graph_conv (:52-68), per sample.
  * dadmm_hyper_linear: y = x W^T + bias (bias nullable). Replaces: the decoder's nn.Linear (:94-104).
  * dadmm_hyper_rownorm: y = LayerNorm(x) over C columns (biased variance), then LeakyReLU(slope)
@@ -488,7 +489,10 @@ int dadmm_hyper_linear_ln(int32_t rows, int32_t K, int32_t N, const float* x, in
  * with layer i's GCN block backward (leaky_relu, per-sample BatchNorm, Dropout, the A_hat mix) in
  * the epilogue: the GEMM's row tiles hold whole samples, so dy never goes to memory. dz, part and
  * every argument after W mean what they mean for dadmm_hyper_gcn_train_bwd; results are
- * bit-identical to dadmm_hyper_linear + dadmm_hyper_gcn_train_bwd. N % 4 == 0, dz 16-byte aligned.
+ * bit-identical to dadmm_hyper_linear + dadmm_hyper_gcn_train_bwd at every shape (ABI 21: its GEMM is
+ * dadmm_hyper_linear's, which never splits its K loop over two wave sets; before, small grids with
+ * 128 <= K < 512 took that split here and differed from the pair by one association per sum).
+ * N % 4 == 0, dz 16-byte aligned.
  * Replaces the pair that follows each of gnn_dlasso_models_progressive.py:52-68's conv_{i+1}
  * blocks in torch's backward. */
 int dadmm_hyper_linear_gcn_bwd(int32_t B, int32_t P, int32_t K, int32_t N, const float* x, int32_t ldx,
@@ -503,6 +507,41 @@ int dadmm_hyper_linear_gcn_bwd(int32_t B, int32_t P, int32_t K, int32_t N, const
 int dadmm_hyper_head_train(int32_t B, int32_t K, int32_t H, const float* x, int32_t ldx, const float* W,
                            const float* bias, float alpha_max, float tau_max, float rho_max, float eta_max,
                            float* z, float* hyp, void* stream);
+/* dadmm_hyper_form (ABI 21): which kernel form a hypernetwork launch of this shape takes in the
+ * current environment (DADMM_GCN32, DADMM_HYPER_KW). Nothing is launched and no GPU is needed; it
+ * asks the planning functions the launches themselves ask. `kind` names the launch:
+ *   LINEAR          dadmm_hyper_linear / _linear_ex: B rows (P unused), K, N, K1;
+ *   GCN             dadmm_hyper_gcn / _gcn_ex: B samples of P nodes;
+ *   HEAD            dadmm_hyper_head / _head_train: B rows, N = 4 H (K1 == K);
+ *   GCN_TRAIN       dadmm_hyper_gcn_train;
+ *   LINEAR_GCN_BWD  dadmm_hyper_linear_gcn_bwd (K1 == K; ks is always 1);
+ *   GCN_BWD         dadmm_hyper_gcn_train_bwd: B, P, N (K, K1 unused).
+ * form: wr = the row tile in units of 32 rows (1, 2, 4, or 5: 160 rows, GCN epilogues only), whole
+ * samples of P rows for the GCN kinds (samples_per_tile of them); dma = the LDS-DMA operand ring
+ * (else each wave's register ring); ks = 2 when the K loop is split over two wave sets, else 1;
+ * split = the input comes in two pieces (K1 < K); gcn32 = the 32x32 inference GCN kernel runs
+ * instead (wr, dma and ks are then 0); nt, pr (GCN_BWD only) = threads per workgroup (64 or 256) and
+ * rows held in registers (8 at P <= 8, else 0); grid = workgroups (0: nothing is launched, B = 0).
+ * Returns DADMM_OK, or the negative DADMM_E* the entry point would return for the shape
+ * (dadmm_last_error() holds its text): DADMM_EINVAL / DADMM_EUNSUPPORTED for what it rejects before
+ * launching, DADMM_EHIP where the launch itself would fail (no tile holds the shape).
+ * P limits: GCN 1..160, GCN_TRAIN 2..137 (one sample's training tile must fit the 160 KB LDS),
+ * LINEAR_GCN_BWD and GCN_BWD 2..64.
+ * Replaces: nothing in the reference (torch_geometric picks no kernel form; :52-68 run per sample). */
+#define DADMM_HYPER_FORM_LINEAR 0
+#define DADMM_HYPER_FORM_GCN 1
+#define DADMM_HYPER_FORM_HEAD 2
+#define DADMM_HYPER_FORM_GCN_TRAIN 3
+#define DADMM_HYPER_FORM_LINEAR_GCN_BWD 4
+#define DADMM_HYPER_FORM_GCN_BWD 5
+typedef struct dadmm_hyper_form_t {
+    int32_t wr, dma, ks, split, gcn32;
+    int32_t nt, pr;
+    int32_t grid, samples_per_tile;
+} dadmm_hyper_form_t;
+int dadmm_hyper_form(int32_t kind, int32_t B, int32_t P, int32_t K, int32_t N, int32_t K1,
+                     dadmm_hyper_form_t* form);
+
 /* ---- GNN hypernetwork, training mode ---------------------------------------------------------
  * The same hypernetwork with model.train() semantics (gnn_dlasso_models_progressive.py:52-72:
  * Dropout(0.1) active, BatchNorm1d on each sample's own batch statistics over its P nodes) and the
@@ -514,7 +553,8 @@ int dadmm_hyper_head_train(int32_t B, int32_t K, int32_t H, const float* x, int3
  *
  * dadmm_hyper_gcn_train: y = Dropout_p(BN_batch(leaky(A_hat (x W^T) + bias))) per sample; saves
  *   m_out [B*P][N] = A_hat (x W^T) + bias and the per-sample mean_out / var_out [B][N] (biased
- *   variance: the normalisation; the caller updates the running statistics). P >= 2, N % 4 == 0.
+ *   variance: the normalisation; the caller updates the running statistics). 2 <= P <= 137 (ABI 21;
+ *   a sample's tile, its saved M and its A_hat must fit the LDS: DADMM_EINVAL beyond), N % 4 == 0.
  *   Replaces: GCNConv + F.leaky_relu + bn_i (train) + self.dropout of graph_conv (:52-68).
  *   ABI 17: with bn_running_mean / bn_running_var (both non-NULL, [N]) the BatchNorm is the eval-mode
  *   one (running statistics; they are written to mean_out / var_out per sample for the backward):

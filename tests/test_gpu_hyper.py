@@ -87,14 +87,23 @@ def _ahat(nbr, P, dev):
                                                 (1024, 50, 400, 400, True), (1024, 50, 100, 200, True),
                                                 (2000, 16, 200, 200, False),
                                                 # small grids (the inference layer never splits K)
-                                                (60, 5, 400, 400, True), (9, 16, 200, 400, False)])
+                                                (60, 5, 400, 400, True), (9, 16, 200, 400, False),
+                                                # a sample of 129..160 nodes on a small grid: one per
+                                                # 160-row tile (pick_tiles's fallback found no tile)
+                                                (3, 130, 64, 68, True), (2, 160, 36, 100, False)])
 def test_gcn_layer_matches_torch(cuda, L, B, P, K, N, per_sample):
     from dadmm_hip.graph import ingest
     G = B if per_sample else 1
     graphs = [O.connected_er_graph(P, 0.4, seed=31 * i + P) for i in range(G)] if P > 1 else \
         [O.er_graph(1, 0.5, seed=0)]
-    gb = ingest(graphs, P, G, cuda)
-    ahat = _ahat(gb.nbr.reshape(G, P), P, cuda)
+    if P > 64:   # no neighbour bit masks: the dense adjacency
+        import gnn_dlasso_models_progressive as GM
+        import networkx as nx
+        adj = torch.from_numpy(np.stack([nx.to_numpy_array(g, nodelist=range(P)) for g in graphs]))
+        ahat = GM.normalized_adjacency(None, P, adj=adj.to(cuda)).contiguous()
+    else:
+        gb = ingest(graphs, P, G, cuda)
+        ahat = _ahat(gb.nbr.reshape(G, P), P, cuda)
     gen = torch.Generator(device=cuda).manual_seed(B * P + N)
     x = torch.randn(B * P, K, device=cuda, generator=gen)
     W = torch.randn(N, K, device=cuda, generator=gen) / np.sqrt(K)

@@ -44,12 +44,25 @@ def _keep(seed, site, rows, cols, p, dev):
     return torch.from_numpy((_drop_hash(seed, site, rows, cols) >= thr).astype(np.float32)).to(dev)
 
 
-def _model(dev, P, n, hidden, mode, seed=0, B=64):
+# A bias ladder for the head's fc: logits far inside and far outside [-9.2, 9.2] (where the
+# clamp(1e-4, 0.9999) binds), at +-89 and +-100 (expf overflows, sigmoid is 0 or 1 in float32). Output
+# i of channel c sits on HEAD_RUNGS[(c + 4 i + i // 4) % 16], so that one row per channel (H = 1)
+# already meets every class of both clamps under the maxima HEAD_MAXIMA_BINDING, whose second clamp
+# (<= 0.9999) binds for tau and eta and sits exactly on its bound for rho.
+HEAD_RUNGS = (-100.0, 100.0, 89.0, -1.3, 12.0, -12.0, 0.4, -89.0, 50.0, -50.0, 6.0, -6.0, 1.7, -0.6, 2.5, -3.0)
+HEAD_MAXIMA_BINDING = (0.1, 1.5, 1.0, 2.0)
+
+
+def _head_ladder(H):
+    return torch.tensor([HEAD_RUNGS[(c + 4 * i + i // 4) % 16] for c in range(4) for i in range(H)])
+
+
+def _model(dev, P, n, hidden, mode, seed=0, B=64, maxima=(0.1, 0.99, 0.99, 0.99)):
     import gnn_dlasso_models_progressive as G
     A, b, _ = O.make_problem(P, 16, n, max(B, 64), seed=seed + 5)
     torch.manual_seed(seed)
-    args = argparse.Namespace(GHN_iter_num=3, GHyp_hidden=hidden, DADMM_mode=mode, alpha_max=0.1,
-                              tau_max=0.99, rho_max=0.99, eta_max=0.99)
+    args = argparse.Namespace(GHN_iter_num=3, GHyp_hidden=hidden, DADMM_mode=mode, alpha_max=maxima[0],
+                              tau_max=maxima[1], rho_max=maxima[2], eta_max=maxima[3])
     model = G.DLASSO_GNNHyp3_Progressive(torch.from_numpy(A)[None].to(dev), args).to(dev)
     with torch.no_grad():
         for i in range(1, 6):
@@ -127,15 +140,32 @@ def _close64(got, want32, want64, name=""):
                                                           (4, 2, 8, "same", False, 6),      # 2n < 4
                                                           # h = 100: the 200/400-deep GEMMs split K
                                                           # over two wave sets (linear_kernel KS = 2)
-                                                          (5, 64, 100, "diff", True, 12)])
-def test_train_hypernetwork_matches_torch_autograd(cuda, P, n, hidden, mode, per_sample, B):
+                                                          (5, 64, 100, "diff", True, 12),
+                                                          # the large-batch defaults (B >= 2048: the tail
+                                                          # kernels, unfused input-gradient GEMMs, the
+                                                          # one-wave gcn_bwd_kernel, row-split weight
+                                                          # gradients); 160-row training tiles on the
+                                                          # 448-wide layers, and at B = 7680 on layer 1
+                                                          # with its hoisted Atb addend too
+                                                          (5, 64, 112, "diff", True, 2250),
+                                                          (5, 64, 112, "diff", False, 7680)])
+def test_train_hypernetwork_matches_torch_autograd(cuda, monkeypatch, P, n, hidden, mode, per_sample, B):
     """n % 4 != 0: layer 1's input cat(AtAy, Atb) zero-padded to a multiple of 4 columns
     (hyper_ops.layer1_input; VERDICT r4 missing #2: such widths ran on torch before)."""
     import copy
 
     import gnn_dlasso_models_progressive as G
-    from dadmm_hip import hyper_ops
+    from dadmm_hip import hyper_form, hyper_ops
     from dadmm_hip.graph import ingest
+    if B >= 2048:   # what the large-batch case is there to run, asked of the launches' own planning
+        for knob in ("DADMM_HYPER_TAIL", "DADMM_GCNBWD_FUSE", "DADMM_HYPER_KW"):
+            monkeypatch.delenv(knob, raising=False)
+        for K, N in ((2 * hidden, 4 * hidden), (4 * hidden, 4 * hidden)):          # conv3, conv4 / conv5
+            assert hyper_form("gcn_train", B, P, K, N)["wr"] == 5, "inputs unsuitable: not the 160-row tile"
+        if B >= 7680:                                                              # conv1 on AtAy (+ addend)
+            assert hyper_form("gcn_train", B, P, n, hidden)["wr"] == 5, "inputs unsuitable: layer 1's tile"
+        for N in (hidden, 2 * hidden, 4 * hidden):
+            assert hyper_form("gcn_bwd", B, P, 4, N)["nt"] == 64, "inputs unsuitable: not the one-wave form"
     model, _, _ = _model(cuda, P, n, hidden, mode)
     ref = copy.deepcopy(model)
     graphs = ([O.connected_er_graph(P, 0.5, seed=s) for s in range(B)] if per_sample
@@ -555,9 +585,14 @@ def test_model_eval_autograd_and_odd_n_use_hip(cuda):
 
 
 @pytest.mark.parametrize("knob", ["DADMM_GCNBWD_FUSE", "DADMM_HYPER_TAIL"])
-@pytest.mark.parametrize("P,n,hidden,B,per_sample", [(5, 64, 16, 40, False), (7, 32, 12, 33, True),
-                                                     (5, 64, 100, 40, True)])
-def test_fused_gcn_backward_bit_identical(cuda, monkeypatch, knob, P, n, hidden, B, per_sample):
+@pytest.mark.parametrize("P,n,hidden,B,per_sample,ladder", [(5, 64, 16, 40, False, False),
+                                                            (7, 32, 12, 33, True, False),
+                                                            (5, 64, 100, 40, True, False),
+                                                            # the head where both of its clamps bind: the
+                                                            # tail kernels restate it (forward and backward)
+                                                            (5, 64, 16, 40, True, True)],
+                         ids=["5-64-16-40-False", "7-32-12-33-True", "5-64-100-40-True", "5-64-16-40-True-ladder"])
+def test_fused_gcn_backward_bit_identical(cuda, monkeypatch, knob, P, n, hidden, B, per_sample, ladder):
     """Two fusions of the training hypernetwork against their separate launches, with dropout on:
     DADMM_GCNBWD_FUSE — GCN layers 4..1's block backward in the epilogue of the layer above's
     input-gradient GEMM (dadmm_hyper_linear_gcn_bwd) vs linear + dadmm_hyper_gcn_train_bwd;
@@ -572,7 +607,11 @@ def test_fused_gcn_backward_bit_identical(cuda, monkeypatch, knob, P, n, hidden,
     import gnn_dlasso_utils as U
     from dadmm_hip import hyper_ops
     from dadmm_hip.graph import ingest
-    model0, _, b = _model(cuda, P, n, hidden, "diff", seed=3, B=B)
+    model0, _, b = _model(cuda, P, n, hidden, "diff", seed=3, B=B,
+                          maxima=HEAD_MAXIMA_BINDING if ladder else (0.1, 0.99, 0.99, 0.99))
+    if ladder:   # fc.bias on the ladder (model.fc's weights are small against it)
+        with torch.no_grad():
+            model0.fc.bias.copy_(_head_ladder(P))
     graphs = ([O.connected_er_graph(P, 0.5, seed=70 + s) for s in range(B)] if per_sample
               else [O.connected_er_graph(P, 0.5, seed=4)] * B)
     gb = ingest(graphs, P, B, cuda)
@@ -603,6 +642,12 @@ def test_fused_gcn_backward_bit_identical(cuda, monkeypatch, knob, P, n, hidden,
                      [p.grad.clone() for p in model.parameters()])
     for got, want in zip(out["1"][0] + out["1"][1], out["0"][0] + out["0"][1]):
         assert torch.equal(got, want), (got - want).abs().max()
+    if ladder:   # the ladder reached the head: saturated lanes on both sides, in and past the second clamp
+        hyp = out["1"][0][len(list(model0.parameters())) + 1]
+        assert torch.isfinite(hyp).all()
+        assert int((hyp[:, 0] == float(np.float32(1e-4) * np.float32(0.1))).sum()) >= B
+        assert int((hyp[:, 1:] == float(np.float32(0.9999))).sum()) >= B
+        assert all(torch.isfinite(t).all() for t in out["1"][0] + out["1"][1])
 
 
 def test_whole_forward_node_guard_raises_in_backward(cuda):
