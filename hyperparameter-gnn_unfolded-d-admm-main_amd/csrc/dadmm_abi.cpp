@@ -827,6 +827,61 @@ int dadmm_loss_grad(int32_t K, int32_t B, int32_t P, int32_t n, int32_t n_store,
     return hip_rc(dadmm::launch_loss_grad(a, gout, dY, (hipStream_t)stream), "loss grad launch");
 }
 
+// ---- the evaluation forward (dadmm_fused_roles.hip, fused_roles_eval_kernel) --------------------
+// its launcher, or nullptr with the reason in dadmm_last_error(): the shapes of the resident
+// role-split form
+static int eval_launcher(const dadmm_dims* d, const uint32_t* nbr_order, dadmm::eval_fn_ptr* fn) {
+    int rc = check_dims(d), graph = 0, nt = 0;
+    if (rc || (rc = check_fused_shape(d, nbr_order, &graph, &nt)) != DADMM_OK) return rc;
+    *fn = dadmm::find_fused_roles_eval(d->P, nt, graph);
+    if (*fn == nullptr)
+        return fail(DADMM_EUNSUPPORTED, "no evaluation kernel for P=%d n=%d (n_pad=%d) graph_shared=%d: it "
+                    "serves P <= 5, n_pad = 256, one shared graph", d->P, d->n, 64 * nt, d->graph_shared);
+    return DADMM_OK;
+}
+static size_t eval_chunks(const dadmm_dims* d) { return 4 * (((size_t)d->B + dadmm::BT - 1) / dadmm::BT); }
+
+size_t dadmm_forward_eval_scratch_bytes(const dadmm_dims* d) {
+    dadmm::eval_fn_ptr fn = nullptr;
+    if (eval_launcher(d, nullptr, &fn) != DADMM_OK || d->B < 1 || d->K < 1) return 0;
+    return align256(sizeof(float) * (size_t)d->K * eval_chunks(d));
+}
+
+int dadmm_forward_eval(const dadmm_dims* d, const void* op, const float* b, const uint64_t* nbr,
+                       const uint32_t* nbr_order, const float* deg, const float* hyp, const float* y0,
+                       const float* U0, const float* d0, const float* label, int32_t n_true,
+                       float* y_final, float* U_out, float* losses, float* out, int32_t* loss_flags,
+                       void* scratch, int32_t* status, void* stream) {
+    int rc = check_dims(d);
+    if (rc) return rc;
+    if (d->B < 1 || d->K < 1) return fail(DADMM_EINVAL, "the evaluation forward needs B >= 1 and K >= 1");
+    if (n_true < 1 || n_true > d->n) return fail(DADMM_EINVAL, "n_true=%d outside 1..n=%d", n_true, d->n);
+    if (any_null(op, b, nbr, deg, hyp, y0, U0, d0, label, y_final, losses, out, loss_flags, scratch))
+        return fail(DADMM_EINVAL, "a required pointer is NULL");
+    if (!aligned16(op)) return fail(DADMM_EINVAL, "op workspace must be 16-byte aligned");
+    if (!all_aligned16(y_final, y0, U0, d0, U_out, label, scratch))
+        return fail(DADMM_EINVAL, "y_final, y0, U0, d0, U_out, label and scratch must be 16-byte aligned");
+    dadmm::eval_fn_ptr fn = nullptr;
+    if ((rc = eval_launcher(d, nbr_order, &fn)) != DADMM_OK) return rc;
+    dadmm::EvalArgs e;
+    fill_fused(e.f, d, op, b, nbr, nbr_order, deg, hyp, y0, U0, d0, y_final, U_out, status);
+    e.label = label;
+    e.partial = (float*)scratch;
+    e.loss_flags = loss_flags;
+    if ((rc = hip_rc(fn(e, (hipStream_t)stream), "evaluation launch")) != DADMM_OK) return rc;
+    dadmm::LossArgs a{};
+    a.partial = e.partial;
+    a.losses = losses;
+    a.out = out;
+    a.flags = loss_flags;
+    a.K = d->K;
+    a.P = d->P;
+    a.n = n_true;
+    a.n_store = d->n;
+    a.rows = (int64_t)d->B * d->P;
+    return hip_rc(dadmm::launch_loss_finish(a, (int)eval_chunks(d), (hipStream_t)stream), "loss finish launch");
+}
+
 // The shape conditions of the hypernetwork GEMMs and their GCN epilogues, shared by the entry
 // points and the dadmm_hyper_form query.
 static int hyper_dims_check(int32_t rows, int32_t K, int32_t N, int32_t K1) {

@@ -265,15 +265,23 @@ __device__ __forceinline__ void roles_matrix(const FusedArgs& a, float* __restri
 }
 
 // ---- update role: waves 4-7 (u = wave - 4) --------------------------------------------------------
-template <int P>
-__device__ __forceinline__ void roles_update(const FusedArgs& a, float* __restrict__ lds, const int u) {
+// EVAL (the evaluation forward, fused_roles_eval_kernel; ev is its EvalArgs, unused otherwise): the
+// same update, and beside it the iterate's squared error against the label. A lane needs the same
+// 16 label rows for every agent and iteration: it parks them in an LDS tile [BT][YS] behind the
+// forward's tiles (written and read by that lane alone: no barrier), sums (y_{k+1} - x)^2 over its
+// P * 16 elements in one fp32 accumulator in the fixed order p, tt, r, and the wave's sum goes to
+// ev->partial[k][4 blockIdx.x + u]. Of the iterates only y_K is stored (a.Y is y_final [B][P][n]).
+template <int P, bool EVAL = false>
+__device__ __forceinline__ void roles_update(const FusedArgs& a, float* __restrict__ lds, const int u,
+                                             const EvalArgs* ev = nullptr) {
     using C = Roles<P, 0>;               // (the LDS layout: the same with and without the resident block)
     constexpr int NP = C::NP, MP = C::MP, YS = C::YS, RS = C::RS, GS = C::GS;
     constexpr int T2 = 4;                // n-tiles of this wave: 4 u + tt
     constexpr int E = T2 * 4;            // state elements per lane per agent
     float* __restrict__ Ylds = lds;
     float* __restrict__ Glds = lds + P * BT * YS + P * BT * RS;
-    (void)NP; (void)MP;
+    float* __restrict__ Llds = Glds + 2 * BT * GS;   // EVAL: [BT][YS] the label rows
+    (void)NP; (void)MP; (void)Llds;
 
     const int lane = threadIdx.x & 63;
     const int j = lane & 15;
@@ -325,6 +333,22 @@ __device__ __forceinline__ void roles_update(const FusedArgs& a, float* __restri
             compiler_fence();            // one tile's loads in flight at a time (register budget)
         }
     }
+    if constexpr (EVAL) {
+        // label [B][n]: rows past n and samples past B read 0, as the state above (there y stays 0
+        // too, so they add exactly 0). Its largest magnitude bits flag a non-finite label as
+        // dadmm_loss.hip's partial_kernel does
+        const rsrc_t rl = make_rsrc(ev->label, (uint32_t)((size_t)B * n * 4));
+        uint32_t lmag = 0;
+#pragma unroll
+        for (int tt = 0; tt < T2; ++tt) {
+            const int n0 = (u * T2 + tt) * 16 + 4 * h;
+            const f32x4 vx = bload4(rl, n0 < n ? (uint32_t)((s * n + n0) * 4) : 0x80000000u, 0);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) lmag = max(lmag, __float_as_uint(vx[r]) & 0x7fffffffu);
+            *(f32x4*)(Llds + j * YS + n0) = vx;
+        }
+        if (__ballot(lmag >= 0x7f800000u) != 0 && lane == 0) atomicOr((unsigned int*)ev->loss_flags, 1u);
+    }
     __syncthreads();                     // y_0 in Ylds: the matrix waves start GEMM1(0)
 
     // dadmm_fused.hip's guards, restated ("The element update"): the y_0 / U_0
@@ -367,11 +391,15 @@ __device__ __forceinline__ void roles_update(const FusedArgs& a, float* __restri
         for (int p = 0; p < P; ++p) load_hyp_row(a, k, p, al[p], ta[p], rh[p], et[p]);
         float gclip, vclip;
         iter_clips(a.variant, k, gclip, vclip);
-        const rsrc_t rY = make_rsrc(a.Y + (size_t)k * B * P * n, state_bytes);
+        // EVAL: one iterate; before the last iteration the range check drops every store
+        const rsrc_t rY = EVAL ? make_rsrc(a.Y, k + 1 == a.K ? state_bytes : 0u)
+                               : make_rsrc(a.Y + (size_t)k * B * P * n, state_bytes);
         const uint32_t vY = fresh(voffY);
         // the largest |gradient| bit pattern seen: above +inf's iff some gradient was NaN (one
         // running register instead of a compare per row that the compiler keeps the rows alive for)
         uint32_t gmag = 0;
+        float acc = 0.0f;                // EVAL: the lane's sum of (y_{k+1} - label)^2
+        (void)acc;
         __syncthreads();                 // stage 0: G_0 is being computed
 
         // primal update of agent p from its G (unfolded_DLASSO.py:73-93); iterate to LDS and Y[k]
@@ -393,7 +421,8 @@ __device__ __forceinline__ void roles_update(const FusedArgs& a, float* __restri
                 compiler_fence();
                 const f32x4 gp = gpb[tt & 1];
                 const f32x4 yk = ykb[tt & 1];   // y_k, 4 rows
-                f32x4 yn;
+                f32x4 yn, xl;
+                if constexpr (EVAL) xl = *(const f32x4*)(Llds + j * YS + n0);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int e = 4 * tt + r;
@@ -401,6 +430,10 @@ __device__ __forceinline__ void roles_update(const FusedArgs& a, float* __restri
                     const float gr = grad_assemble(gp[r], yv, U[p][e], D[p][e], ta[p], dg[p], rh[p]);
                     gmag = max(gmag, __float_as_uint(gr) & 0x7fffffffu);   // :84 guard (flag only)
                     yn[r] = primal_elem<Clamp::MED3>(yv, gr, al[p], gclip, vclip);
+                    if constexpr (EVAL) {
+                        const float d = yn[r] - xl[r];
+                        acc += d * d;
+                    }
                 }
                 gmag = fresh(gmag);      // folded here, not sunk to the loop's end with every row alive
                 *(f32x4*)(Ylds + (p * BT + j) * YS + n0) = yn;
@@ -412,6 +445,10 @@ __device__ __forceinline__ void roles_update(const FusedArgs& a, float* __restri
             __syncthreads();             // stages 1..P
         }
         status |= gmag > 0x7f800000u ? DADMM_STATUS_GRAD_NAN : 0;
+        if constexpr (EVAL) {
+            const float wsum = wave_sum_dpp(acc);
+            if (lane == 0) ev->partial[(size_t)k * (gridDim.x * 4) + blockIdx.x * 4 + u] = wsum;
+        }
 
         // delta_{k+1} = 2 L y_{k+1} for the lane's rows (all agents, lane-local), GNN delta clamp,
         // U_{k+1} = clamp(U_k + delta_{k+1} * eta_k) (:95-99). After the last iteration only U_out
@@ -469,6 +506,14 @@ __device__ __forceinline__ void roles_update(const FusedArgs& a, float* __restri
     }
 }
 
+// This file is compiled twice (csrc/Makefile), like dadmm_fused.hip: as it stands for the forward's
+// kernels, and with DADMM_ROLES_EVAL=1 for the evaluation forward's alone, so that the forward's
+// compile unit is the same with and without the evaluation kernels beside it.
+#ifndef DADMM_ROLES_EVAL
+#define DADMM_ROLES_EVAL 0
+#endif
+
+#if !DADMM_ROLES_EVAL
 template <int P, int RES>
 __global__ __launch_bounds__(FUSED_WAVES * 64) void fused_roles_kernel(FusedArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[Roles<P, RES>::LDS_FLOATS];
@@ -500,5 +545,41 @@ fused_fn_ptr find_fused_roles(int P, int nt, int graph, bool resident) {
         default: return nullptr;
     }
 }
+
+#else   // DADMM_ROLES_EVAL
+// The evaluation forward: the resident form's matrix role unchanged, the update
+// role with EVAL and its label tile behind the forward's LDS tiles
+template <int P>
+__global__ __launch_bounds__(FUSED_WAVES * 64) void fused_roles_eval_kernel(EvalArgs e) {
+    __shared__ __attribute__((aligned(16))) float lds[Roles<P, 1>::LDS_FLOATS + BT * Roles<P, 1>::YS];
+    static_assert(sizeof(lds) <= 160 * 1024, "the label tile beside the forward's tiles");
+    static_assert(FUSED_WAVES == 8, "one matrix wave and one update wave per SIMD");
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (w < 4)
+        roles_matrix<P, 1>(e.f, lds, w);
+    else
+        roles_update<P, true>(e.f, lds, w - 4, &e);
+}
+
+template <int P>
+static hipError_t launch_roles_eval(const EvalArgs& e, hipStream_t stream) {
+    const int grid = (e.f.B + BT - 1) / BT;
+    hipLaunchKernelGGL((fused_roles_eval_kernel<P>), dim3(grid), dim3(FUSED_WAVES * 64), 0, stream, e);
+    return hipGetLastError();
+}
+
+// The shapes of the resident role-split form; nullptr otherwise.
+eval_fn_ptr find_fused_roles_eval(int P, int nt, int graph) {
+    if (nt != 4 || graph != GRAPH_SHARED) return nullptr;
+    switch (P) {
+        case 1: return &launch_roles_eval<1>;
+        case 2: return &launch_roles_eval<2>;
+        case 3: return &launch_roles_eval<3>;
+        case 4: return &launch_roles_eval<4>;
+        case 5: return &launch_roles_eval<5>;
+        default: return nullptr;
+    }
+}
+#endif
 
 }  // namespace dadmm

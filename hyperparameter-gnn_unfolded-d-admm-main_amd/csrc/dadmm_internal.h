@@ -69,6 +69,20 @@ fused_fn_ptr find_fused_rec(int P, int nt, int graph);
 // whole launch (the default form), or every operand fragment streamed.
 fused_fn_ptr find_fused_roles(int P, int nt, int graph, bool resident);
 
+// The evaluation forward (dadmm_fused_roles.hip, fused_roles_eval_kernel): the resident role-split
+// forward that sums every iterate's squared error against the label where it holds the iterate in
+// registers and stores only the last one. f is the forward's argument block, layout unchanged, with
+// f.Y = y_final [B][P][n] (one iterate, not K).
+struct EvalArgs {
+    FusedArgs f;
+    const float* label;  // [B][n] (n = f.n: the stored row length, padding columns zero)
+    float* partial;      // [K][4 * ceil(B / BT)] per-wave sums of (y_{k+1} - label)^2
+    int32_t* loss_flags; // [2] as LossArgs::flags; word 0 zeroed before the launch
+};
+typedef hipError_t (*eval_fn_ptr)(const EvalArgs&, hipStream_t);
+// The shapes find_fused_roles serves (P = 1..5, nt = 4, GRAPH_SHARED); nullptr otherwise.
+eval_fn_ptr find_fused_roles_eval(int P, int nt, int graph);
+
 // ---- the column-split forward for small batches (dadmm_split.hip) ------------------------------
 constexpr int SPLIT_COLS = 64;   // columns of n_pad per slice (one workgroup each)
 struct SplitArgs {
@@ -235,6 +249,9 @@ struct LossArgs {
 };
 size_t loss_scratch_floats(int K, int64_t rows, int n);
 hipError_t launch_loss(const LossArgs& a, hipStream_t st);
+// finish_kernel alone over a.partial [K][nch] that another kernel wrote (the evaluation forward):
+// reads a.partial, a.flags[0], a.K, a.rows, a.n; writes a.losses, a.out, a.flags[1]
+hipError_t launch_loss_finish(const LossArgs& a, int nch, hipStream_t st);
 hipError_t launch_loss_grad(const LossArgs& a, const float* gout, float* dY, hipStream_t st);
 
 // ---- GNN hypernetwork, inference mode (dadmm_hyper.hip) ------------------------------------------

@@ -154,6 +154,11 @@ hipError_t launch_loss(const LossArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
+hipError_t launch_loss_finish(const LossArgs& a, int nch, hipStream_t st) {
+    hipLaunchKernelGGL(loss::finish_kernel, dim3(1), dim3(loss::THREADS), 0, st, a, nch);
+    return hipGetLastError();
+}
+
 hipError_t launch_loss_grad(const LossArgs& a, const float* gout, float* dY, hipStream_t st) {
     const int64_t total = (int64_t)a.rows * a.n_store;
     if (total >= ((int64_t)1 << 31)) return hipErrorInvalidValue;

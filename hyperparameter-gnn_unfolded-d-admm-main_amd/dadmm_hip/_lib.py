@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # scripts/time_variants.sh); it is still the HIP library, there is no other path
 LIB_PATH = os.environ.get("DADMM_LIB_VARIANT") or os.path.join(_HERE, "libdadmm.so")
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 DADMM_OK, DADMM_EINVAL, DADMM_EUNSUPPORTED, DADMM_EHIP = 0, -1, -2, -3
 VARIANT_UNFOLDED, VARIANT_GNN = 0, 1
 STATUS_Y_NONFINITE, STATUS_U_NONFINITE, STATUS_GRAD_NAN, STATUS_YNEXT_NAN = 1, 2, 4, 8
@@ -89,6 +89,8 @@ EXPORTED_SYMBOLS = (
     "dadmm_loss_scratch_bytes",
     "dadmm_loss",
     "dadmm_loss_grad",
+    "dadmm_forward_eval_scratch_bytes",
+    "dadmm_forward_eval",
 )
 
 
@@ -234,6 +236,10 @@ def load() -> ctypes.CDLL:
     L.dadmm_loss.argtypes = [i32] * 5 + [vp] * 7
     L.dadmm_loss_grad.restype = ctypes.c_int
     L.dadmm_loss_grad.argtypes = [i32] * 5 + [vp] * 6
+    L.dadmm_forward_eval_scratch_bytes.restype = ctypes.c_size_t
+    L.dadmm_forward_eval_scratch_bytes.argtypes = [D]
+    L.dadmm_forward_eval.restype = ctypes.c_int
+    L.dadmm_forward_eval.argtypes = [D] + [vp] * 10 + [i32] + [vp] * 8
     L.dadmm_gnn_flag_bytes.restype = ctypes.c_size_t
     L.dadmm_gnn_flag_bytes.argtypes = [i32]
     for name, args in (("dadmm_gnn_begin", [D] + [vp] * 7),

@@ -303,6 +303,82 @@ def tiled_form(dims_or_shape, record: bool = False) -> int:
     return int(_lib.load().dadmm_tiled_form(ctypes.byref(d), 1 if record else 0))
 
 
+def eval_served(dims_or_op, B: int, K: int, graphs: GraphBatch = None) -> bool:
+    """Whether the evaluation forward (forward_eval_raw, dadmm_forward_eval) serves the shape
+    (dadmm_forward_eval_scratch_bytes != 0; no GPU needed): P <= 5, 128 < n <= 256, m <= 64 and
+    one shared graph. dims_or_op: a ``PreparedOperator`` or a ``_lib.Dims`` (whose B, K and
+    graph_shared are replaced). graphs None: a shared graph."""
+    if graphs is not None and not (graphs.shared and graphs.fused_ok):
+        return False
+    o = dims_or_op
+    n = o.n_store if isinstance(o, PreparedOperator) else (o.n + 3) & ~3
+    d = _lib.Dims(B=B, P=o.P, m=o.m, n=n, K=K, variant=_lib.VARIANT_UNFOLDED, hyp_rows=1,
+                  graph_shared=1)
+    return _lib.load().dadmm_forward_eval_scratch_bytes(ctypes.byref(d)) != 0
+
+
+def forward_eval_raw(op: PreparedOperator, b: torch.Tensor, graphs: GraphBatch, hyp: torch.Tensor,
+                     label: torch.Tensor, y0: torch.Tensor = None, U0: torch.Tensor = None,
+                     d0: torch.Tensor = None, *, variant: int = _lib.VARIANT_UNFOLDED,
+                     want_U: bool = False):
+    """The K-step forward and the drivers' loss on its iterates (gnn_dlasso_utils.compute_loss,
+    reference gnn_dlasso_utils.py:27-88) without storing the iterates: the role-split kernel sums
+    every iterate's squared error against ``label`` [B,n] where it holds the iterate in registers
+    and stores only the last one. Three launches on the current stream (prologue, evaluation
+    kernel, loss finish), no host synchronisation, one scratch allocation.
+
+    Like forward_raw's forced paths it does NOT apply the reference's guards: ``status`` flags
+    them, and without the iterates nothing here can recompute the batch (DLASSO_unfolded.evaluate
+    does, through the ordinary forward). y0 = U0 = d0 = None: drawn by the prologue launch exactly
+    as forward_raw draws them (same values, same generator advance).
+
+    Returns (losses [K], out [2] = (loss_mean, loss_final) with the reference's (1, 1) fallback,
+    y_final [B,P,n] = forward_raw's Y[-1] bit for bit, U_K [B,P,n] or None, status int32 [1],
+    loss_flags int32 [2] (non-finite label seen, fallback fired), (y0, U0, d0) as used).
+    Raises ValueError where ``eval_served`` is False."""
+    _dev_check(b, hyp, label, y0, U0, d0, graphs.nbr, graphs.deg)
+    draw = y0 is None
+    if draw != (U0 is None) or draw != (d0 is None):
+        raise ValueError("pass all of y0, U0, d0 or none of them")
+    B, P, m = b.shape
+    if P != op.P or m != op.m:
+        raise ValueError(f"b is [B,{P},{m}], operator is P={op.P}, m={op.m}")
+    K, H = int(hyp.shape[0]), int(hyp.shape[1])
+    if not eval_served(op, B, K, graphs):
+        raise ValueError(f"the evaluation forward does not serve B={B} K={K} P={P} m={m} n={op.n} "
+                         "(P <= 5, 128 < n <= 256, m <= 64, one shared graph the fused kernel follows)")
+    if label.numel() != B * op.n:
+        raise ValueError(f"label must hold [B={B}, n={op.n}] values, got {tuple(label.shape)}")
+    ns, dev, L = op.n_store, b.device, _lib.load()
+    d = op.dims(B=B, K=K, variant=variant, hyp_rows=H, graph_shared=1)
+    with torch.cuda.device(dev):
+        b, hyp = b.contiguous().float(), hyp.contiguous().float()
+        label = _pad_n(label.reshape(B, op.n).float(), ns).contiguous()
+        y_final = torch.empty((B, P, ns), dtype=torch.float32, device=dev)
+        U = torch.empty((B, P, ns), dtype=torch.float32, device=dev) if want_U else None
+        res = torch.empty(K + 2, dtype=torch.float32, device=dev)      # losses, then out
+        # one allocation: [status word | 12 B pad | loss flags (2 words) | pad to 256 B | partial
+        # sums]; the prologue zeroes the first 256 B in the same launch as the draws
+        words = torch.empty(256 + L.dadmm_forward_eval_scratch_bytes(ctypes.byref(d)),
+                            dtype=torch.uint8, device=dev)
+        status, flags = words[:4].view(torch.int32), words[16:24].view(torch.int32)
+        if draw:
+            y0, U0, d0 = draw_inits((B, P, op.n), dev, ns, zero=words, nzero=64)
+        else:
+            y0, U0, d0 = (_pad_n(x, ns).contiguous().float() for x in (y0, U0, d0))
+            _lib.check("dadmm_prologue", L.dadmm_prologue(
+                0, 0, 0, 1, 1, 0.0, 0.0, None, None, None, _ptr(words), 64, _stream(dev)))
+        _lib.check("dadmm_forward_eval", L.dadmm_forward_eval(
+            ctypes.byref(d), _ptr(op.workspace), _ptr(b), _ptr(graphs.nbr), None, _ptr(graphs.deg),
+            _ptr(hyp), _ptr(y0), _ptr(U0), _ptr(d0), _ptr(label), op.n, _ptr(y_final), _ptr(U),
+            _ptr(res), _ptr(res[K:]), _ptr(flags), _ptr(words[256:]), _ptr(status), _stream(dev)))
+    if ns != op.n:
+        y_final = y_final[..., : op.n]
+        U = U[..., : op.n] if U is not None else None
+        y0, U0, d0 = (x[..., : op.n] for x in (y0, U0, d0))
+    return res[:K], res[K:], y_final, U, status, flags, (y0, U0, d0)
+
+
 def hyper_form(kind: str, B: int, P: int, K: int, N: int, K1=None):
     """Which kernel form a hypernetwork launch takes (dadmm_hyper_form; no GPU needed, nothing
     launched). kind: "linear", "gcn", "head", "gcn_train", "linear_gcn_bwd" (B samples of P nodes;

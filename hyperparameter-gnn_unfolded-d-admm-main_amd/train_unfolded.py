@@ -77,8 +77,13 @@ def validate(model, b_va, x_va, graph, args, bs, gen, rank, world, device):
         for idx in _batches(args.test_size, bs, gen, shuffle=True):
             lo, hi = D.shard_range(bs, rank, world)
             sel = idx[lo:hi].to(device)
-            Y, hyp = model(b_va[sel], [graph] * (hi - lo), inits=_inits(args, bs, lo, hi, device))
-            loss_mean, loss_final = gnn_dlasso_utils.compute_loss(Y, x_va[sel])
+            if getattr(args, "fused_eval", False):   # callers with their own args: off
+                ev = model.evaluate(b_va[sel], [graph] * (hi - lo), x_va[sel],
+                                    inits=_inits(args, bs, lo, hi, device))
+                loss_mean, loss_final, hyp = ev.loss_mean, ev.loss_final, ev.hyp
+            else:
+                Y, hyp = model(b_va[sel], [graph] * (hi - lo), inits=_inits(args, bs, lo, hi, device))
+                loss_mean, loss_final = gnn_dlasso_utils.compute_loss(Y, x_va[sel])
             # the timeout flag rides in the loss all_reduce: every rank raises together
             tot += float(D.global_losses(loss_mean, loss_final, hi - lo,
                                          timed_out=timed_out(loss_final))[1])
@@ -101,6 +106,12 @@ def build_parser():
                          "256) run the recording column-split kernel "
                          "(DLASSO_unfolded.train_split): the iterates then follow the split GEMM1 "
                          "order, which differs from the fused order in fp32 rounding")
+    ap.add_argument("--fused-eval", action="store_true",
+                    help="validation batches go through DLASSO_unfolded.evaluate: where the "
+                         "evaluation kernel serves (one shared graph, P <= 5, 128 < n <= 256, "
+                         "m <= 64) the losses are summed inside the fused forward and the K "
+                         "iterates are never stored; elsewhere the same forward and compute_loss "
+                         "as without the flag")
     return ap
 
 

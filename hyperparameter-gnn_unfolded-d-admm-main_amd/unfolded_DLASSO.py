@@ -8,6 +8,8 @@ recurrence runs in one fused HIP launch (``dadmm_hip``, C ABI ``include/dadmm.h`
 """
 from __future__ import annotations
 
+import collections
+
 import torch
 import torch.nn as nn
 
@@ -17,6 +19,10 @@ from dadmm_hip.autograd import check_status, dadmm_unfolded_apply, tag_status
 from dadmm_hip.ops import describe_status
 from dadmm_hip.graph import ingest, n_graphs
 from dadmm_hip.ops import PreparedOperator
+
+# what DLASSO_unfolded.evaluate returns
+Evaluation = collections.namedtuple("Evaluation",
+                                    "losses loss_mean loss_final y_final hyp status")
 
 
 class DLASSO_unfolded(nn.Module):
@@ -134,6 +140,81 @@ class DLASSO_unfolded(nn.Module):
                                                    train_split=bool(self.train_split))
         hyp = table[K - 1].unsqueeze(-1)                # seq_hyp(K-1): [H, 4, 1]
         return tag_status(Y.unsqueeze(-1), self.last_status), hyp
+
+    def evaluate(self, b, graph_list, label, K=None, *, inits=None, on_guard="recompute"):
+        """The validation step in one call: ``forward(b, graph_list, K)``, then
+        ``gnn_dlasso_utils.compute_loss(Y, label)`` and ``layer_losses`` (the reference's loop,
+        unfolded_train_new.py:102-125), without the iterates. label [B,n,1] or [B,n].
+
+        Returns ``Evaluation(losses [K'], loss_mean, loss_final, y_final [B,P,n,1], hyp [H,4,1],
+        status)``: the per-iterate losses, compute_loss's two scalars (with the reference's (1, 1)
+        fallback), the last iterate, seq_hyp(K'-1) and the device status word. K' = min(K, self.K),
+        the memoised table and the graph ingestion are forward's. No gradient flows: with a table
+        that requires grad under enabled grad it raises (use ``forward`` to train).
+
+        Where the evaluation kernel serves (CUDA tensors, one shared graph the fused kernel
+        follows, P <= 5, 128 < n <= 256, m <= 64: ``dadmm_hip.ops.eval_served``) the K iterates
+        are never stored: the losses are summed inside the fused forward (three launches, memory
+        for a K times larger batch). Its losses equal compute_loss's up to fp32 summation order;
+        y_final equals forward's Y[-1] bit for bit. A guard event cannot be repaired there, since
+        the stepwise recomputation uses Y as its state:
+
+          on_guard="recompute" (default) reads the 4-byte status word at the end: ONE host
+            synchronisation (the drivers' validation loops synchronise on that word anyway,
+            through ``timed_out`` on the next line). If any bit is set, an asymmetric shared
+            adjacency's DADMM_STATUS_RECOMPUTE included, the batch is rerun through ``forward``
+            with the same draws plus compute_loss: the result is that path's, bit for bit.
+          on_guard="flag" never synchronises: where status != 0 the losses and y_final are NaN,
+            selected on the device, and the status word rides on them (``timed_out`` /
+            ``raise_if_timed_out`` read it).
+
+        Everywhere else (CPU tensors, per-sample or ordered graphs, other shapes) it runs
+        ``forward`` plus ``compute_loss`` plus ``layer_losses`` and returns the same tuple: same
+        values as those calls, and NO memory saving."""
+        import gnn_dlasso_utils
+        from dadmm_hip.ops import eval_served, forward_eval_raw
+        if on_guard not in ("recompute", "flag"):
+            raise ValueError(f"on_guard must be 'recompute' or 'flag', got {on_guard!r}")
+        if torch.is_grad_enabled() and self.seq_hyp.param.requires_grad:
+            raise RuntimeError("evaluate() computes no gradient: call it under torch.no_grad() "
+                               "(or with a frozen table); training goes through forward() and "
+                               "gnn_dlasso_utils.compute_loss")
+        batch_size = max(len(b), n_graphs(graph_list, len(b)))
+        Kp = self.K if K is None else min(K, self.K)
+
+        def through_forward(inits):
+            with torch.no_grad():
+                Y, hyp = self.forward(b, graph_list, K, inits=inits)
+                loss_mean, loss_final = gnn_dlasso_utils.compute_loss(Y, label)
+                losses = gnn_dlasso_utils.layer_losses(Y, label.reshape(batch_size, self.n))
+            return Evaluation(losses, loss_mean, loss_final, Y[-1], hyp, self.last_status)
+
+        served = (b.device.type == "cuda" and Kp > 0 and b.dim() == 4 and len(b) == batch_size
+                  and b.shape[1] == self.P and b.shape[2] == self.m)
+        if served:
+            graphs = ingest(graph_list, self.P, batch_size, b.device)
+            served = eval_served(self.operator(), batch_size, Kp, graphs)
+        if not served:
+            return through_forward(inits)
+
+        with torch.no_grad():
+            table = self.hyp_table(Kp)
+            y0, U0, d0 = (None,) * 3 if inits is None else (
+                x.reshape(batch_size, self.P, self.n) for x in inits)
+            losses, out, y_final, _, status, _, used = forward_eval_raw(
+                self.operator(), b[..., 0], graphs, table, label, y0, U0, d0)
+            self.last_status = status
+            if on_guard == "recompute":
+                if check_status(status) != 0:      # the one host synchronisation
+                    return through_forward(used)
+            else:
+                bad = status.reshape(-1)[0] != 0
+                nan = torch.full((), float("nan"), dtype=torch.float32, device=b.device)
+                losses, out, y_final = (torch.where(bad, nan, t) for t in (losses, out, y_final))
+            hyp = table[Kp - 1].unsqueeze(-1)
+            return Evaluation(tag_status(losses, status), tag_status(out[0], status),
+                              tag_status(out[1], status), tag_status(y_final.unsqueeze(-1), status),
+                              hyp, status)
 
     def guard_warnings(self):
         """The reference's NaN/Inf warnings (unfolded_DLASSO.py:56-104) for the last forward

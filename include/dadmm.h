@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define DADMM_ABI_VERSION 21
+#define DADMM_ABI_VERSION 22
 
 enum {
     DADMM_OK = 0,
@@ -418,6 +418,32 @@ int dadmm_loss(int32_t K, int32_t B, int32_t P, int32_t n, int32_t n_store, cons
 int dadmm_loss_grad(int32_t K, int32_t B, int32_t P, int32_t n, int32_t n_store, const float* Y,
                     const float* label, const int32_t* flags, const float* gout, float* dY,
                     void* stream);
+
+/* ---- the forward and the loss in one pass, no stored iterates (ABI 22) --------------------------
+ * The validation loops run the forward, compute_loss and keep two scalars
+ * (unfolded_train_new.py:102-125); their progression plots keep the K per-iterate losses. This is
+ * dadmm_forward + dadmm_loss for that use: the role-split forward sums (y_{k+1} - label)^2 where
+ * it holds y_{k+1} in registers and stores only the last iterate, then dadmm_loss's finish.
+ * Replaces: the same loop as dadmm_forward (unfolded_DLASSO.py:45, 53-109) without torch.stack(Y)
+ *           (:109), and compute_loss (gnn_dlasso_utils.py:27-88) with its (1, 1) fallback
+ *           (:36-43, :69-71, :83-86).
+ * Shapes: the role-split form's (P <= 5, n_pad = 256, m <= 64, graph_shared = 1, nbr_order NULL):
+ *   dadmm_forward_eval_scratch_bytes is 0 elsewhere (no GPU needed) and dadmm_forward_eval returns
+ *   DADMM_EUNSUPPORTED.
+ * label [B][n] with n = d->n, the stored row length: the caller zero-pads the columns past
+ * n_true, as it does y0 / U0 / d0; n_true is the loss's denominator (B P n_true).
+ * y_final [B][P][n] = Y[K-1] of dadmm_forward, U_out and status as there, bit for bit.
+ * losses [K], out [2], loss_flags [2] as dadmm_loss; losses differ from dadmm_loss's in fp32
+ * summation order only (per-wave fp32 sums in a fixed order, then the same double finish).
+ * `status` and `loss_flags` must be ZERO at the call (the prologue's `zero` words can clear them);
+ * scratch: dadmm_forward_eval_scratch_bytes(d) bytes, 16-byte aligned, any content.
+ * Two launches; allocates nothing; no host synchronisation; deterministic. */
+size_t dadmm_forward_eval_scratch_bytes(const dadmm_dims* d);
+int dadmm_forward_eval(const dadmm_dims* d, const void* op, const float* b, const uint64_t* nbr,
+                       const uint32_t* nbr_order, const float* deg, const float* hyp, const float* y0,
+                       const float* U0, const float* d0, const float* label, int32_t n_true,
+                       float* y_final, float* U_out, float* losses, float* out, int32_t* loss_flags,
+                       void* scratch, int32_t* status, void* stream);
 
 /* ---- GNN hypernetwork, inference mode ---------------------------------------------------------
  * GNNHypernetwork3 + decoder + fc of DLASSO_GNNHyp3_Progressive (gnn_dlasso_models_progressive.py

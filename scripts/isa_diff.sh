@@ -1,6 +1,6 @@
 #!/bin/bash
 # isa_diff.sh REV — is the gfx950 device code of the working tree the same as REV's?
-# Compiles every csrc/*.hip (and the two recording builds) of REV, from a temporary git worktree,
+# Compiles every csrc/*.hip (and the second builds: recording, evaluation) of REV, from a temporary git worktree,
 # and of the working tree to device assembly with the Makefile's flags, and diffs them file by
 # file. Only the translation-unit id __hip_cuid_<hex> (a hash of the source text) is erased.
 # Prints `identical` or the first lines of the diff per file, and for a file that differs one line
@@ -18,6 +18,9 @@ units() {   # "name source extra-flag" per compile unit of the tree $1
     for f in "$1/$SUB"/*.hip; do echo "$(basename "$f" .hip) $f"; done
     echo "dadmm_fused_rec $1/$SUB/dadmm_fused.hip -DDADMM_FUSED_REC=1"
     echo "dadmm_split_rec $1/$SUB/dadmm_split.hip -DDADMM_SPLIT_REC=1"
+    if grep -q DADMM_ROLES_EVAL "$1/$SUB/dadmm_fused_roles.hip"; then   # the evaluation kernels' build
+        echo "dadmm_fused_roles_eval $1/$SUB/dadmm_fused_roles.hip -DDADMM_ROLES_EVAL=1"
+    fi
 }
 mkdir "$TMP/a" "$TMP/b"
 { units "$TMP/old" | sed "s|^|$TMP/a |"; units "$ROOT" | sed "s|^|$TMP/b |"; } |
