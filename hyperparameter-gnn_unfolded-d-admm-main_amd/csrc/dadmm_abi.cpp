@@ -882,6 +882,85 @@ int dadmm_forward_eval(const dadmm_dims* d, const void* op, const float* b, cons
     return hip_rc(dadmm::launch_loss_finish(a, (int)eval_chunks(d), (hipStream_t)stream), "loss finish launch");
 }
 
+// ---- the streamed evaluation forward (dadmm_stream.hip built with DADMM_STREAM_EVAL) -------------
+// Served where the streamed single launch applies as it does for recording (the 8-wave forms,
+// whatever DADMM_TILED_STREAM / DADMM_STREAM_WAVES say) and dadmm_forward has no kernel: on the
+// fused shapes the fused forward is the faster one, and DLASSO_unfolded.evaluate stays on it there.
+static int eval_stream_check(const dadmm_dims* d, dadmm::TiledArgs* a) {
+    int rc = check_dims(d);
+    if (rc) return rc;
+    if (d->B < 1 || d->K < 1) return fail(DADMM_EINVAL, "the evaluation forward needs B >= 1 and K >= 1");
+    if ((rc = tiled_shape_check(d)) != DADMM_OK) return rc;
+    *a = dadmm::TiledArgs{};
+    fill_args_padded(*a, d, nullptr);
+    const bool fused_shape = d->m <= dadmm::M_PAD && a->n_pad <= 256 && (d->P <= 5 || (d->P == 6 && a->n_pad <= 128));
+    if (fused_shape)
+        return fail(DADMM_EUNSUPPORTED, "P=%d m=%d n=%d (n_pad=%d) is a shape of dadmm_forward: the streamed "
+                    "evaluation serves P > 6, P = 6 at n_pad > 128, n_pad > 256 or m > 64", d->P, d->m, d->n, a->n_pad);
+    if (!dadmm::stream_eval_applies(*a))
+        return fail(DADMM_EUNSUPPORTED, "no streamed evaluation kernel for P=%d m=%d n=%d (n_pad=%d): it serves "
+                    "P <= 16 at m <= 64, P <= 8 at m <= 128, n_pad >= 128", d->P, d->m, d->n, a->n_pad);
+    if ((size_t)d->K * dadmm::stream_eval_chunks(d->B) * 4 >= ((size_t)1 << 31))
+        return fail(DADMM_EUNSUPPORTED, "K*8*ceil(B/16)*4 >= 2^31 bytes of partial sums (split the batch)");
+    return DADMM_OK;
+}
+
+size_t dadmm_forward_eval_stream_scratch_bytes(const dadmm_dims* d) {
+    dadmm::TiledArgs a;
+    if (eval_stream_check(d, &a) != DADMM_OK) return 0;
+    // the U state, the second iterate, the partial sums
+    return 2 * align256(sizeof(float) * (size_t)d->B * d->P * d->n) +
+           align256(sizeof(float) * (size_t)d->K * dadmm::stream_eval_chunks(d->B));
+}
+
+int dadmm_forward_eval_stream(const dadmm_dims* d, const void* op, const float* b, const int32_t* visit_ptr,
+                              const uint8_t* visit_q, const float* deg, const float* hyp, const float* y0,
+                              const float* U0, const float* d0, const float* label, int32_t n_true,
+                              float* y_final, float* U_out, float* losses, float* out, int32_t* loss_flags,
+                              void* scratch, int32_t* status, void* stream) {
+    dadmm::StreamEvalArgs e{};
+    int rc = eval_stream_check(d, &e.t);
+    if (rc) return rc;
+    if (n_true < 1 || n_true > d->n) return fail(DADMM_EINVAL, "n_true=%d outside 1..n=%d", n_true, d->n);
+    if (any_null(op, b, visit_ptr, visit_q, deg, hyp, y0, U0, d0, label, y_final, losses, out, loss_flags, scratch))
+        return fail(DADMM_EINVAL, "a required pointer is NULL");
+    if (!all_aligned16(op, y_final, y0, U0, d0, U_out, label))
+        return fail(DADMM_EINVAL, "op, y_final, y0, U0, d0, U_out and label must be 16-byte aligned");
+    if ((rc = check_scratch256(scratch)) != DADMM_OK) return rc;
+    const size_t state = align256(sizeof(float) * (size_t)d->B * d->P * d->n);
+    fill_args_padded(e.t, d, op);
+    e.t.b = b;
+    e.t.vptr = visit_ptr;
+    e.t.vq = visit_q;
+    e.t.deg = deg;
+    e.t.hyp = hyp;
+    e.t.y0 = y0;
+    e.t.U0 = U0;
+    e.t.d0 = d0;
+    e.t.Y = y_final;
+    e.t.Ubuf[0] = (float*)scratch;
+    e.t.U_out = U_out;
+    e.t.status = status;
+    e.label = label;
+    e.ybuf = (float*)((char*)scratch + state);
+    e.partial = (float*)((char*)scratch + 2 * state);
+    e.loss_flags = loss_flags;
+    if ((rc = hip_rc(dadmm::launch_stream_eval(e, (hipStream_t)stream), "streamed evaluation launch")) != DADMM_OK)
+        return rc;
+    dadmm::LossArgs a{};
+    a.partial = e.partial;
+    a.losses = losses;
+    a.out = out;
+    a.flags = loss_flags;
+    a.K = d->K;
+    a.P = d->P;
+    a.n = n_true;
+    a.n_store = d->n;
+    a.rows = (int64_t)d->B * d->P;
+    return hip_rc(dadmm::launch_loss_finish(a, dadmm::stream_eval_chunks(d->B), (hipStream_t)stream),
+                  "loss finish launch");
+}
+
 // The shape conditions of the hypernetwork GEMMs and their GCN epilogues, shared by the entry
 // points and the dadmm_hyper_form query.
 static int hyper_dims_check(int32_t rows, int32_t K, int32_t N, int32_t K1) {

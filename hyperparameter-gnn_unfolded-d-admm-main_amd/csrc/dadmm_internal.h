@@ -236,6 +236,24 @@ bool stream_applies(const TiledArgs& a);
 int tiled_form(const TiledArgs& a, bool record);
 hipError_t launch_stream(const TiledArgs& a, hipStream_t stream);
 
+// The evaluation form of the streamed forward (dadmm_stream.hip built with DADMM_STREAM_EVAL,
+// stream_eval_kernel): the same walk with two iterates of state that take turns instead of K, and
+// every iterate's squared error against the label summed where the iterate is in registers. t is
+// the forward's argument block, layout unchanged, with t.Y = y_final [B][P][n] (one iterate) and
+// t.Ubuf[0] the U state; t.Grec / t.Urec stay NULL.
+struct StreamEvalArgs {
+    TiledArgs t;
+    const float* label;  // [B][n] (n = t.n: the stored row length, padding columns zero)
+    float* ybuf;         // [B][P][n] scratch: the iterates Y[k] with K - 1 - k odd
+    float* partial;      // [K][stream_eval_chunks(B)] per-wave sums of (y_{k+1} - label)^2
+    int32_t* loss_flags; // [2] as LossArgs::flags; word 0 zeroed before the launch
+};
+// the 8-wave streamed forms' shapes (P <= 16 at m_pad 64, P <= 8 at m_pad 128, n_pad >= 128),
+// independent of the environment switches that choose among the forward's forms
+bool stream_eval_applies(const TiledArgs& a);
+int stream_eval_chunks(int B);   // 8 * ceil(B / BT)
+hipError_t launch_stream_eval(const StreamEvalArgs& e, hipStream_t stream);
+
 // ---- fused loss (dadmm_loss.hip) ----------------------------------------------------------------
 struct LossArgs {
     const float* Y;         // [K][rows][n_store], rows = B * P

@@ -30,6 +30,33 @@
 // of the reference's batch-global NaN/Inf guards would fire, and the caller's gated stepwise
 // recomputation redoes such a batch exactly. On guard-free inputs the output is bit-identical to
 // oracle_forward_f32 and to the other paths.
+//
+// The evaluation form (EVAL; stream_eval_kernel, built alone with DADMM_STREAM_EVAL=1, DESIGN.md
+// §4.11b) is the same walk with two iterates of state instead of K and the drivers' loss summed
+// where y_{k+1} is in registers. Y[k] goes to the caller's y_final when K - 1 - k is even and to the
+// scratch state ybuf otherwise, so y_K lands in y_final for odd and even K, and the DMA of phase k
+// reads where Y[k - 1] went (y0 at k = 0, never written). Why two buffers that take turns are safe:
+//   * a wave reads (LDS-DMA) and writes only the rows of its own agents, and a workgroup only its
+//     own 16 samples: no other wave ever touches the rows a wave overwrites;
+//   * vector-memory operations of a wave complete in issue order;
+//   * phase k + 1 is the first to store into the buffer that holds Y[k - 1]; its first store is
+//     issued in its step 0, behind that step's wait_prev_step, and the last DMA that reads Y[k - 1]
+//     (the block of phase k's last step, issued two steps before it) was awaited by wait_prev_step
+//     at the top of that last step of phase k: every read of Y[k - 1] has completed before the
+//     first byte of it is overwritten;
+//   * Y[k] itself is read back as before: its block NB - 2 >= 2 steps after it was written, behind
+//     the wait_prev_step that covers the stores of two steps earlier.
+// The label is the same for every agent and iteration. Its rows of the whole tile in LDS (16 rows of
+// n_pad = 512 are 32 KB) do not fit beside the ring and the visit rows, 135 KB of the 160 KB at
+// P = 16, and a register load per tile is four more VGPRs live across the walk and GEMM2, where the
+// two 256-VGPR forms have none to spare. So the step's label block (16 samples x 32 columns, 2 KB)
+// rides with the step's y block: one more LDS-DMA per wave and step into a label ring of the same
+// three slots (7 KB), read back by one ds_read_b128 where the update has y_{k+1}: one load per
+// (step, column tile) serves every agent of every wave.
+// wait_prev_step's counts are lower bounds on what a step issues, so the extra copy per step (and
+// the one partial-sum store per phase) keeps them valid: a wait for fewer outstanding operations
+// than the step issued only covers more of the older ones, never fewer; and the label slot is
+// covered by the same wait and barrier as the y slot it shares its step with.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -95,7 +122,7 @@ __host__ __device__ constexpr int vt_stride(int P) {
     return 4 * (((2 * P + 3) / 4) | 1);
 }
 constexpr int slot_floats(int NWT, int PW) { return NWT * PW * CT * 64 * 4; }
-size_t lds_bytes(int NWT, int PW, int P) {
+inline size_t lds_bytes(int NWT, int PW, int P) {
     const int PA = NWT * PW;
     return 4 * (size_t)SLOTS * slot_floats(NWT, PW) + 4 * (size_t)PA * BT * vt_stride(P) + 4 * (size_t)PA;
 }
@@ -129,8 +156,36 @@ __device__ __forceinline__ void wait_prev_step(int kprev, int K) {
     else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
 }
 
+// This file is compiled twice (csrc/Makefile), like dadmm_fused_roles.hip: as it stands for the
+// forward's and the recording kernels, and with DADMM_STREAM_EVAL=1 for the evaluation kernels
+// alone (the same body under another kernel head: EVAL is a constant of the build, not one more
+// template parameter, which would rename every forward kernel), so that the forward's compile unit
+// is the same with and without them beside it.
+#ifndef DADMM_STREAM_EVAL
+#define DADMM_STREAM_EVAL 0
+#endif
+// EVAL only: the label block of a step (16 samples x 32 columns, 2 KB) rides in a ring of its own
+// behind the visit rows, slot for slot with the y ring, plus one spare KB (label_dma)
+constexpr int LAB_FLOATS = CT * 64 * 4;
+inline size_t eval_lds_bytes(int NWT, int PW, int P) {
+    return lds_bytes(NWT, PW, P) + 4 * (size_t)(SLOTS * LAB_FLOATS + 64 * 4);
+}
+
+#if !DADMM_STREAM_EVAL
 template <int NWT, int PW, bool REC = false, int MB = 1>
 __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
+    constexpr bool EVAL = false;
+    const StreamEvalArgs* const ev = nullptr;
+#else
+// a.Y is y_final [B][P][n], one iterate; the wave's sum of (y_{k+1} - label)^2 of phase k goes to
+// ev->partial[k][8 blockIdx.x + w]
+template <int NWT, int PW, bool REC = false, int MB = 1>
+__global__ __launch_bounds__(64 * NWT) void stream_eval_kernel(StreamEvalArgs e) {
+    constexpr bool EVAL = true;
+    const TiledArgs& a = e.t;
+    const StreamEvalArgs* const ev = &e;
+    static_assert(NWT == 8 && !REC, "evaluation: the 8-wave forms, never recording");
+#endif
     static_assert(MB == 1 || (MB == 2 && NWT == 8 && PW == 1), "two m-groups: one agent per wave, 8 waves");
     constexpr int NW = NWT;
     constexpr int MT = 4 * MB;        // 16-row blocks per agent
@@ -144,6 +199,8 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
     const int DP = vt_stride(P);
     uint32_t* vt = (uint32_t*)(lds + SLOTS * SF);        // [PA][BT][DP] visit rows (byte offsets)
     int* dmx = (int*)(vt + PA * BT * DP);                // [PA] longest row of each agent
+    float* lab = (float*)(dmx + PA);                     // EVAL: [SLOTS][LAB_FLOATS] label ring + 1 KB
+    (void)lab;
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int j = lane & 15, bq = lane >> 4;             // sample in the tile, 4-column group
@@ -192,6 +249,8 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
     // offset past the range, which the hardware returns as zeros)
     auto dma = [&](int k, int blk, float* slot) {
         const float* src = k <= 0 ? a.y0 : a.Y + (size_t)(k - 1) * S;
+        if constexpr (EVAL)   // where Y[k - 1] went: the base selected, then one descriptor built
+            src = k <= 0 ? a.y0 : (((K - k) & 1) != 0 ? ev->ybuf : a.Y);
         const i32x4 r = rsrc_words(src, (k <= kend) ? s_bytes : 0u);
 #pragma unroll
         for (int ai = 0; ai < PW; ++ai) {
@@ -202,6 +261,19 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
                                          ? (uint32_t)(elem(q, blk * CW, ct) * 4) : 0x80000000u;
                 dma16((uint32_t)(uintptr_t)(lds_void*)(slot + 4 * ((q * CT + ct) * 64)), off, r);
             }
+        }
+        if constexpr (EVAL) {
+            // the step's label block (the same for every agent and iteration) into the label ring's
+            // slot, chunk (ct, bq, j) like a y tile's: wave ct < CT copies 16-column tile ct. One
+            // unconditional instruction per wave: the other waves copy nothing (a zero-size
+            // descriptor, as every phase without a primal update) into the spare KB no lane reads.
+            const bool mine = w < CT;
+            const int lct = mine ? w : 0;
+            float* dst = mine ? lab + (int)((slot - lds) / SF) * LAB_FLOATS + 4 * 64 * lct : lab + SLOTS * LAB_FLOATS;
+            const i32x4 rl = rsrc_words(ev->label, (mine && k >= 0 && k < K) ? (uint32_t)((size_t)B * n * 4) : 0u);
+            const uint32_t off = col_ok(blk * CW, lct)
+                                     ? (fresh((uint32_t)sc) * n + blk * CW + 16 * lct + 4 * bq) * 4 : 0x80000000u;
+            dma16((uint32_t)(uintptr_t)(lds_void*)dst, off, rl);
         }
     };
     // operator buffers: per-lane offsets fixed for the whole launch, the rest in SGPRs
@@ -272,9 +344,11 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
         const int pc = pin ? p : 0;
         const bool ok = k < K - 1 && pin;
 #pragma unroll
-        for (int t = 4 * g; t < 4 * g + 4; ++t)
-            r.am[t] = bload4(dA, ok ? vam + (uint32_t)(16 * t * NP * 4) : 0x80000000u,
-                             (uint32_t)((((size_t)pc * MP) * NP + c0 + 16 * ct) * 4));
+        for (int t = 4 * g; t < 4 * g + 4; ++t) {
+            const uint32_t rstep = (uint32_t)(16 * t * NP * 4);   // (EVAL: in soffset, see fetch_m)
+            r.am[t] = bload4(dA, ok ? vam + (EVAL ? 0u : rstep) : 0x80000000u,
+                             (uint32_t)((((size_t)pc * MP) * NP + c0 + 16 * ct) * 4) + (EVAL ? rstep : 0u));
+        }
     };
     auto fetch_m = [&](int k, int c0, int i, Ring& r) {
         const int ai = i / CT, ct = i % CT;
@@ -283,9 +357,15 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
         const int pc = pin ? p : 0;
         const bool ok = k < K - 1 && pin;
 #pragma unroll
-        for (int t = 0; t < 4; ++t)
-            r.am[t] = bload4(dA, ok ? vam + (uint32_t)(16 * t * NP * 4) : 0x80000000u,
-                             (uint32_t)((((size_t)pc * 64) * NP + c0 + 16 * ct) * 4));
+        for (int t = 0; t < 4; ++t) {
+            // EVAL: the row step rides in soffset like the A^T rows' (the range check sees the
+            // lane's offset only), one lane offset for the four loads instead of four registers:
+            // what frees the evaluation forms of every spill. The forward keeps it in the lane
+            // offset: its instructions are pinned until it is measured again.
+            const uint32_t rstep = (uint32_t)(16 * t * NP * 4);
+            r.am[t] = bload4(dA, ok ? vam + (EVAL ? 0u : rstep) : 0x80000000u,
+                             (uint32_t)((((size_t)pc * 64) * NP + c0 + 16 * ct) * 4) + (EVAL ? rstep : 0u));
+        }
     };
 
     f32x4 Rk[PW][MT], Rn[PW][MT];
@@ -296,6 +376,14 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
     bool bad_y0 = false, bad_u0 = false, bad_g = false, bad_y = false, bad_h = false;
     float al[PW], ta[PW], rh[PW], etp[PW];
     float gclip = 0.0f, vclip = 0.0f, vclip_prev = 0.0f;
+    // EVAL: the lane's sum of (y_{k+1} - label)^2 over the phase, in the order of its tiles, and
+    // whether a label value it read was non-finite (a lane mask in SGPRs like the guards above; the
+    // role-split kernel's running maximum of the magnitude bits is one more VGPR, which the
+    // 256-VGPR forms do not have)
+    float lacc = 0.0f;
+    bool bad_l = false;
+    (void)lacc;
+    (void)bad_l;
 
     // tile i of step bs (phase k, columns c0), operands in r; pre() issues the next tile's A^T rows,
     // U and d0 after the consensus walk, mid() its A rows after GEMM2. With two m-groups the next
@@ -387,7 +475,27 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
             bad_y |= upd && okc && !finitef(v);
             yn[r4] = okc ? v : 0.0f;
         }
-        bstore4(yn, make_rsrc(a.Y + (size_t)(upd ? k : 0) * S, s_bytes), upd ? soff : 0x80000000u);
+        if constexpr (EVAL) {
+            // Y[k] -> y_final when K - 1 - k is even, else the scratch state (the header has why the
+            // two may take turns); the base selected, then the descriptor built
+            bstore4(yn, make_rsrc(((K - 1 - k) & 1) != 0 ? ev->ybuf : a.Y, s_bytes), upd ? soff : 0x80000000u);
+            // the label of the lane's sample at the tile's columns, from the label ring's slot of
+            // this step (zeros outside an updating phase, past B and past n); the squared error:
+            // three roundings per term, one chain per lane. A lane without a
+            // stored element (an absent agent p >= P, whose lanes still belong to a real sample with
+            // a real label; a sample past B; columns past n; phases -1 and K) adds exactly +0: the
+            // select is under the Y store's own predicate
+            const f32x4 xl = *(const f32x4*)(lab + (int)((ys - lds) / SF) * LAB_FLOATS + 4 * (ct * 64 + lane));
+#pragma unroll
+            for (int r4 = 0; r4 < 4; ++r4) {
+                const float d = yn[r4] - xl[r4];
+                const float t = d * d;
+                lacc += (upd && okc) ? t : 0.0f;
+            }
+            bad_l |= !finite4(xl);
+        } else {
+            bstore4(yn, make_rsrc(a.Y + (size_t)(upd ? k : 0) * S, s_bytes), upd ? soff : 0x80000000u);
+        }
         if constexpr (REC) {   // the adjoint's trajectory: Grec[k] (pre-clamp gradient), Urec[k] = U_k
             const size_t kS = (size_t)(upd ? k : 0) * S;
             bstore4(grc, make_rsrc(a.Grec + kS, s_bytes), upd ? soff : 0x80000000u);
@@ -449,8 +557,13 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
 #pragma unroll
                 for (int t = 0; t < MT; ++t) Rk[ai][t] = Rn[ai][t];
         }
+        if constexpr (EVAL) lacc = 0.0f;
         {   // (unconditional: Rn is dead in phases K - 1 and K)
             const bool bk = k < K - 1;
+            // EVAL: the lane's row group opaque per phase, so that the 16 * MB * PW row offsets below
+            // are computed here and not hoisted out of the phase loop as as many registers (there
+            // they were spilled: the evaluation forms have no register to spare for them)
+            const int bqk = EVAL ? (int)fresh((uint32_t)bq) : bq;
 #pragma unroll
             for (int ai = 0; ai < PW; ++ai) {
                 const int p = w + NW * ai;
@@ -458,7 +571,7 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
                 for (int t = 0; t < MT; ++t)
 #pragma unroll
                     for (int r4 = 0; r4 < 4; ++r4) {
-                        const int row = 16 * t + 4 * bq + r4;
+                        const int row = 16 * t + 4 * bqk + r4;
                         const uint32_t boff = (bk && sok && p < P && row < m)
                                                   ? (uint32_t)((((size_t)s * P + p) * m + row) * 4) : 0x80000000u;
                         Rn[ai][t][r4] = -__builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(db, boff, 0, 0));
@@ -513,6 +626,19 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
             }
             slot = slot == SLOTS - 1 ? 0 : slot + 1;
         }
+        if constexpr (EVAL) {
+            // the wave's sum of the phase -> partial[k][8 blockIdx.x + w]: a plain vector store,
+            // every lane but 0 and the phases -1 and K at an out-of-range offset
+            const float wsum = wave_sum_dpp(lacc);
+            const uint32_t nch = NW * gridDim.x;
+            const uint32_t poff = (k >= 0 && k < K && lane == 0)
+                                      ? (uint32_t)(((size_t)k * nch + NW * blockIdx.x + w) * 4) : 0x80000000u;
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, wsum),
+                                                  make_rsrc(ev->partial, (uint32_t)((size_t)K * nch * 4)), poff, 0, 0);
+        }
+    }
+    if constexpr (EVAL) {   // a non-finite label: bit 0 of loss_flags[0], one atomic per wave
+        if (__ballot(bad_l) != 0 && lane == 0) atomicOr((unsigned int*)ev->loss_flags, 1u);
     }
     status |= (bad_y0 ? DADMM_STATUS_Y_NONFINITE : 0) | (bad_u0 ? DADMM_STATUS_U_NONFINITE : 0) |
               (bad_g ? DADMM_STATUS_GRAD_NAN : 0) | ((bad_y || bad_h) ? DADMM_STATUS_YNEXT_NAN : 0);
@@ -526,6 +652,7 @@ __global__ __launch_bounds__(64 * NWT) void stream_kernel(TiledArgs a) {
 
 }  // namespace stream
 
+#if !DADMM_STREAM_EVAL
 // The streamed single-launch form applies to P <= 16 agents with m <= 64 rows each, or P <= 8 agents
 // with 64 < m <= 128 (two m-groups, one agent per wave: stream_kernel<8, 1, ., 2>), and at least
 // four 32-column blocks (the ring reads Y[k - 1]'s block >= 2 steps after it was written).
@@ -598,5 +725,37 @@ hipError_t launch_stream(const TiledArgs& a, hipStream_t st) {
         hipLaunchKernelGGL((stream::stream_kernel<8, 2>), dim3(grid), dim3(64 * 8), lds, st, a);
     return hipGetLastError();
 }
+
+#else   // DADMM_STREAM_EVAL
+// The evaluation form serves the shapes of the 8-wave streamed forms, whatever DADMM_TILED_STREAM /
+// DADMM_STREAM_WAVES say (they choose among forward forms; there is one evaluation form): P <= 16 at
+// m_pad = 64, P <= 8 at m_pad = 128, at least four 32-column blocks.
+bool stream_eval_applies(const TiledArgs& a) {
+    const bool rows = a.m_pad == 64 || (a.m_pad == 128 && a.P <= stream::NW);
+    return rows && a.P >= 1 && a.P <= 2 * stream::NW && a.n_pad % stream::CW == 0 &&
+           a.n_pad / stream::CW >= 4 &&
+           stream::eval_lds_bytes(stream::NW, (a.P + stream::NW - 1) / stream::NW, a.P) <= 160 * 1024;
+}
+
+int stream_eval_chunks(int B) { return stream::NW * ((B + BT - 1) / BT); }
+
+template <int PW, int MB>
+static hipError_t launch_eval(const StreamEvalArgs& e, hipStream_t st) {
+    const int grid = (e.t.B + BT - 1) / BT;
+    const size_t lds = stream::eval_lds_bytes(stream::NW, PW, e.t.P);
+    hipError_t err = hipFuncSetAttribute((const void*)stream::stream_eval_kernel<stream::NW, PW, false, MB>,
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL((stream::stream_eval_kernel<stream::NW, PW, false, MB>), dim3(grid), dim3(64 * stream::NW),
+                       lds, st, e);
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_eval(const StreamEvalArgs& e, hipStream_t st) {
+    if (!stream_eval_applies(e.t)) return hipErrorInvalidValue;
+    if (e.t.m_pad == 128) return launch_eval<1, 2>(e, st);
+    return e.t.P <= stream::NW ? launch_eval<1, 1>(e, st) : launch_eval<2, 1>(e, st);
+}
+#endif
 
 }  // namespace dadmm

@@ -8,8 +8,9 @@ repo's ``train_unfolded.py`` / ``train_gnn.py`` (INTEGRATION.md).
 """
 from . import _lib
 from .graph import GraphBatch, from_csr, generate_er, ingest, to_networkx
-from .ops import PreparedOperator, eval_served, forward_eval_raw, forward_raw, hyper_form, tiled_form
+from .ops import (PreparedOperator, eval_served, eval_stream_served, forward_eval_raw,
+                  forward_eval_stream_raw, forward_raw, hyper_form, tiled_form)
 
 __all__ = ["_lib", "GraphBatch", "from_csr", "generate_er", "ingest", "to_networkx",
-           "PreparedOperator", "eval_served", "forward_eval_raw", "forward_raw", "hyper_form",
-           "tiled_form"]
+           "PreparedOperator", "eval_served", "eval_stream_served", "forward_eval_raw",
+           "forward_eval_stream_raw", "forward_raw", "hyper_form", "tiled_form"]

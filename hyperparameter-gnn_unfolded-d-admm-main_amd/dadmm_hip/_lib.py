@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # scripts/time_variants.sh); it is still the HIP library, there is no other path
 LIB_PATH = os.environ.get("DADMM_LIB_VARIANT") or os.path.join(_HERE, "libdadmm.so")
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 DADMM_OK, DADMM_EINVAL, DADMM_EUNSUPPORTED, DADMM_EHIP = 0, -1, -2, -3
 VARIANT_UNFOLDED, VARIANT_GNN = 0, 1
 STATUS_Y_NONFINITE, STATUS_U_NONFINITE, STATUS_GRAD_NAN, STATUS_YNEXT_NAN = 1, 2, 4, 8
@@ -91,6 +91,8 @@ EXPORTED_SYMBOLS = (
     "dadmm_loss_grad",
     "dadmm_forward_eval_scratch_bytes",
     "dadmm_forward_eval",
+    "dadmm_forward_eval_stream_scratch_bytes",
+    "dadmm_forward_eval_stream",
 )
 
 
@@ -240,6 +242,10 @@ def load() -> ctypes.CDLL:
     L.dadmm_forward_eval_scratch_bytes.argtypes = [D]
     L.dadmm_forward_eval.restype = ctypes.c_int
     L.dadmm_forward_eval.argtypes = [D] + [vp] * 10 + [i32] + [vp] * 8
+    L.dadmm_forward_eval_stream_scratch_bytes.restype = ctypes.c_size_t
+    L.dadmm_forward_eval_stream_scratch_bytes.argtypes = [D]
+    L.dadmm_forward_eval_stream.restype = ctypes.c_int
+    L.dadmm_forward_eval_stream.argtypes = [D] + [vp] * 10 + [i32] + [vp] * 8
     L.dadmm_gnn_flag_bytes.restype = ctypes.c_size_t
     L.dadmm_gnn_flag_bytes.argtypes = [i32]
     for name, args in (("dadmm_gnn_begin", [D] + [vp] * 7),

@@ -122,6 +122,16 @@ class ForwardPlan:
 # (DESIGN.md §4.7b has the sweep); path="tiled" takes it at every batch size.
 STREAM_RECORD_M128_MIN_B = 4096
 
+# The same trade for DLASSO_unfolded.evaluate at m > 64: the streamed evaluation launch (two
+# m-groups, one workgroup per 16 samples) against forward + compute_loss on the per-iteration
+# launches, which is what forward runs there by default. The module routes to the streamed
+# evaluation only from this batch size on; forward_eval_stream_raw serves every batch size.
+# Measured at P = 5, m = 100, n = 500, K = 25 (scripts/time_eval_stream.py, DESIGN.md §4.11b,
+# profiles/r14/time_eval_stream_default_sweep_r14.json), ms per validation step, evaluate against
+# forward + compute_loss: B = 32: 2.84 / 1.13, 256: 2.85 / 1.22, 1024: 2.89 / 1.40, 2048: 2.93 /
+# 2.50, 4096: 3.01 / 3.83. Every evaluate round is below every baseline round at 4096 only.
+STREAM_EVAL_M128_MIN_B = 4096
+
 
 def plan_forward(d: _lib.Dims, fused_ok: bool, *, path: str = "auto", record: bool = False,
                  train_split: bool = False) -> ForwardPlan:
@@ -372,6 +382,80 @@ def forward_eval_raw(op: PreparedOperator, b: torch.Tensor, graphs: GraphBatch, 
             ctypes.byref(d), _ptr(op.workspace), _ptr(b), _ptr(graphs.nbr), None, _ptr(graphs.deg),
             _ptr(hyp), _ptr(y0), _ptr(U0), _ptr(d0), _ptr(label), op.n, _ptr(y_final), _ptr(U),
             _ptr(res), _ptr(res[K:]), _ptr(flags), _ptr(words[256:]), _ptr(status), _stream(dev)))
+    if ns != op.n:
+        y_final = y_final[..., : op.n]
+        U = U[..., : op.n] if U is not None else None
+        y0, U0, d0 = (x[..., : op.n] for x in (y0, U0, d0))
+    return res[:K], res[K:], y_final, U, status, flags, (y0, U0, d0)
+
+
+def eval_stream_served(dims_or_op, B: int, K: int, graphs: GraphBatch = None) -> bool:
+    """Whether the streamed evaluation forward (forward_eval_stream_raw, dadmm_forward_eval_stream)
+    serves the shape (dadmm_forward_eval_stream_scratch_bytes != 0; no GPU needed): the streamed
+    single launch's shapes (P <= 16 at m <= 64, P <= 8 at m <= 128, n_pad >= 128) that the fused
+    forward has no kernel for (P > 6, P = 6 at n_pad > 128, n_pad > 256 or m > 64), with shared or
+    per-sample graphs. dims_or_op: a ``PreparedOperator`` or a ``_lib.Dims`` (whose B, K and
+    graph_shared are replaced). graphs None: a shared graph; otherwise it must carry the visit
+    lists of at most 16 agents."""
+    o = dims_or_op
+    if graphs is not None and (graphs.vptr is None or graphs.vq is None or o.P > 16):
+        return False
+    n = o.n_store if isinstance(o, PreparedOperator) else (o.n + 3) & ~3
+    d = _lib.Dims(B=B, P=o.P, m=o.m, n=n, K=K, variant=_lib.VARIANT_UNFOLDED, hyp_rows=1,
+                  graph_shared=1 if graphs is None else int(graphs.shared))
+    return _lib.load().dadmm_forward_eval_stream_scratch_bytes(ctypes.byref(d)) != 0
+
+
+def forward_eval_stream_raw(op: PreparedOperator, b: torch.Tensor, graphs: GraphBatch,
+                            hyp: torch.Tensor, label: torch.Tensor, y0: torch.Tensor = None,
+                            U0: torch.Tensor = None, d0: torch.Tensor = None, *,
+                            variant: int = _lib.VARIANT_UNFOLDED, want_U: bool = False):
+    """forward_eval_raw on the streamed forward (csrc/dadmm_stream.hip's evaluation kernels): the
+    K-step forward and the drivers' loss on its iterates with two iterates of state (y_final and
+    one in scratch, taking turns) instead of K. Same arguments, same contract (the guards are only
+    flagged in ``status``; drawn inits as forward_raw draws them) and same return tuple as
+    forward_eval_raw; y_final equals forward_raw's Y[-1] bit for bit. Three launches on the
+    current stream (prologue, evaluation kernel, loss finish), no host synchronisation, one scratch
+    allocation. It serves every batch size; raises ValueError where ``eval_stream_served`` is
+    False."""
+    _dev_check(b, hyp, label, y0, U0, d0, graphs.vptr, graphs.deg)
+    draw = y0 is None
+    if draw != (U0 is None) or draw != (d0 is None):
+        raise ValueError("pass all of y0, U0, d0 or none of them")
+    B, P, m = b.shape
+    if P != op.P or m != op.m:
+        raise ValueError(f"b is [B,{P},{m}], operator is P={op.P}, m={op.m}")
+    K, H = int(hyp.shape[0]), int(hyp.shape[1])
+    if not eval_stream_served(op, B, K, graphs):
+        raise ValueError(f"the streamed evaluation forward does not serve B={B} K={K} P={P} m={m} "
+                         f"n={op.n} (P <= 16 at m <= 64, P <= 8 at m <= 128, n_pad >= 128, and no "
+                         "shape of the fused forward: P > 6, P = 6 at n > 128, n > 256 or m > 64)")
+    if label.numel() != B * op.n:
+        raise ValueError(f"label must hold [B={B}, n={op.n}] values, got {tuple(label.shape)}")
+    ns, dev, L = op.n_store, b.device, _lib.load()
+    d = op.dims(B=B, K=K, variant=variant, hyp_rows=H, graph_shared=graphs.shared)
+    with torch.cuda.device(dev):
+        b, hyp = b.contiguous().float(), hyp.contiguous().float()
+        label = _pad_n(label.reshape(B, op.n).float(), ns).contiguous()
+        y_final = torch.empty((B, P, ns), dtype=torch.float32, device=dev)
+        U = torch.empty((B, P, ns), dtype=torch.float32, device=dev) if want_U else None
+        res = torch.empty(K + 2, dtype=torch.float32, device=dev)      # losses, then out
+        # one allocation: [status word | 12 B pad | loss flags (2 words) | pad to 256 B | U state |
+        # second iterate | partial sums]; the prologue zeroes the first 256 B with the draws
+        words = torch.empty(256 + L.dadmm_forward_eval_stream_scratch_bytes(ctypes.byref(d)),
+                            dtype=torch.uint8, device=dev)
+        status, flags = words[:4].view(torch.int32), words[16:24].view(torch.int32)
+        if draw:
+            y0, U0, d0 = draw_inits((B, P, op.n), dev, ns, zero=words, nzero=64)
+        else:
+            y0, U0, d0 = (_pad_n(x, ns).contiguous().float() for x in (y0, U0, d0))
+            _lib.check("dadmm_prologue", L.dadmm_prologue(
+                0, 0, 0, 1, 1, 0.0, 0.0, None, None, None, _ptr(words), 64, _stream(dev)))
+        _lib.check("dadmm_forward_eval_stream", L.dadmm_forward_eval_stream(
+            ctypes.byref(d), _ptr(op.workspace), _ptr(b), _ptr(graphs.vptr), _ptr(graphs.vq),
+            _ptr(graphs.deg), _ptr(hyp), _ptr(y0), _ptr(U0), _ptr(d0), _ptr(label), op.n,
+            _ptr(y_final), _ptr(U), _ptr(res), _ptr(res[K:]), _ptr(flags), _ptr(words[256:]),
+            _ptr(status), _stream(dev)))
     if ns != op.n:
         y_final = y_final[..., : op.n]
         U = U[..., : op.n] if U is not None else None

@@ -109,9 +109,11 @@ def build_parser():
     ap.add_argument("--fused-eval", action="store_true",
                     help="validation batches go through DLASSO_unfolded.evaluate: where the "
                          "evaluation kernel serves (one shared graph, P <= 5, 128 < n <= 256, "
-                         "m <= 64) the losses are summed inside the fused forward and the K "
-                         "iterates are never stored; elsewhere the same forward and compute_loss "
-                         "as without the flag")
+                         "m <= 64) or the streamed forward's evaluation form does (P <= 16 at "
+                         "m <= 64, P <= 8 at m <= 128, n > 64, outside the fused shapes; the "
+                         "default shape P 5, m 100, n 500 from a batch threshold on) the losses "
+                         "are summed inside the forward and the K iterates are never stored; "
+                         "elsewhere the same forward and compute_loss as without the flag")
     return ap
 
 

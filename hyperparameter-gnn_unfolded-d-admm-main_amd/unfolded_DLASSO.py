@@ -168,11 +168,21 @@ class DLASSO_unfolded(nn.Module):
             selected on the device, and the status word rides on them (``timed_out`` /
             ``raise_if_timed_out`` read it).
 
-        Everywhere else (CPU tensors, per-sample or ordered graphs, other shapes) it runs
+        Where that kernel does not serve but the streamed forward's evaluation form does (CUDA
+        tensors, shared or per-sample graphs, P <= 16 at m <= 64 or P <= 8 at m <= 128, n > 64, and
+        no shape of the fused forward: P > 6, P = 6 at n > 128, n > 256 or m > 64:
+        ``dadmm_hip.ops.eval_stream_served``; BASELINE configs[2] and the reference's default
+        shape P = 5, m = 100, n = 500 are such shapes) the same holds with two iterates of state
+        instead of K, the same three launches and the same two ``on_guard`` policies. At m > 64 it
+        is taken from a batch of ``dadmm_hip.ops.STREAM_EVAL_M128_MIN_B`` on: below it the
+        forward's per-iteration launches are the faster step.
+
+        Everywhere else (CPU tensors, ordered graphs on fused shapes, other shapes) it runs
         ``forward`` plus ``compute_loss`` plus ``layer_losses`` and returns the same tuple: same
         values as those calls, and NO memory saving."""
         import gnn_dlasso_utils
-        from dadmm_hip.ops import eval_served, forward_eval_raw
+        from dadmm_hip import ops
+        from dadmm_hip.ops import eval_served, eval_stream_served, forward_eval_raw, forward_eval_stream_raw
         if on_guard not in ("recompute", "flag"):
             raise ValueError(f"on_guard must be 'recompute' or 'flag', got {on_guard!r}")
         if torch.is_grad_enabled() and self.seq_hyp.param.requires_grad:
@@ -191,9 +201,13 @@ class DLASSO_unfolded(nn.Module):
 
         served = (b.device.type == "cuda" and Kp > 0 and b.dim() == 4 and len(b) == batch_size
                   and b.shape[1] == self.P and b.shape[2] == self.m)
+        eval_raw = forward_eval_raw
         if served:
             graphs = ingest(graph_list, self.P, batch_size, b.device)
             served = eval_served(self.operator(), batch_size, Kp, graphs)
+            if not served and eval_stream_served(self.operator(), batch_size, Kp, graphs):
+                served = self.m <= 64 or batch_size >= ops.STREAM_EVAL_M128_MIN_B
+                eval_raw = forward_eval_stream_raw
         if not served:
             return through_forward(inits)
 
@@ -201,7 +215,7 @@ class DLASSO_unfolded(nn.Module):
             table = self.hyp_table(Kp)
             y0, U0, d0 = (None,) * 3 if inits is None else (
                 x.reshape(batch_size, self.P, self.n) for x in inits)
-            losses, out, y_final, _, status, _, used = forward_eval_raw(
+            losses, out, y_final, _, status, _, used = eval_raw(
                 self.operator(), b[..., 0], graphs, table, label, y0, U0, d0)
             self.last_status = status
             if on_guard == "recompute":

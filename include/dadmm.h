@@ -57,7 +57,7 @@
 extern "C" {
 #endif
 
-#define DADMM_ABI_VERSION 22
+#define DADMM_ABI_VERSION 23
 
 enum {
     DADMM_OK = 0,
@@ -444,6 +444,30 @@ int dadmm_forward_eval(const dadmm_dims* d, const void* op, const float* b, cons
                        const float* U0, const float* d0, const float* label, int32_t n_true,
                        float* y_final, float* U_out, float* losses, float* out, int32_t* loss_flags,
                        void* scratch, int32_t* status, void* stream);
+
+/* ---- the same on the streamed forward (ABI 23) ---------------------------------------------------
+ * dadmm_forward_eval for the shapes dadmm_forward has no kernel for and the streamed single launch
+ * of dadmm_forward_tiled serves: P <= 16 at m <= 64, P <= 8 at 64 < m <= 128, n_pad >= 128, and
+ * P > 6, or P = 6 at n_pad > 128, or n_pad > 256, or m > 64 (BASELINE configs[2]: P = 16, n = 512;
+ * the reference's default shape P = 5, m = 100, n = 500); shared or per-sample graphs, given as
+ * dadmm_forward_tiled's visit lists. Elsewhere dadmm_forward_eval_stream_scratch_bytes is 0 (no GPU
+ * needed) and the entry point returns DADMM_EUNSUPPORTED with the reason in dadmm_last_error(). The
+ * choice does not read DADMM_TILED_STREAM / DADMM_STREAM_WAVES: there is one evaluation form.
+ * The streamed kernel keeps two iterates that take turns (y_final and one in scratch) instead of K,
+ * and sums (y_{k+1} - label)^2 where it holds y_{k+1} in registers; then dadmm_loss's finish.
+ * label, n_true, y_final, U_out, losses, out, loss_flags, status: as dadmm_forward_eval (`status`
+ * and `loss_flags` ZERO at the call; label zero-padded to n = d->n; y_final = Y[K-1] of
+ * dadmm_forward_tiled bit for bit).
+ * scratch: dadmm_forward_eval_stream_scratch_bytes(d) bytes, 256-byte aligned, any content: the U
+ *   state, the second iterate, the [K][8 ceil(B/16)] per-wave partial sums, each 256-byte aligned.
+ * Two launches; allocates nothing; no host synchronisation; deterministic. */
+size_t dadmm_forward_eval_stream_scratch_bytes(const dadmm_dims* d);
+int dadmm_forward_eval_stream(const dadmm_dims* d, const void* op, const float* b,
+                              const int32_t* visit_ptr, const uint8_t* visit_q, const float* deg,
+                              const float* hyp, const float* y0, const float* U0, const float* d0,
+                              const float* label, int32_t n_true, float* y_final, float* U_out,
+                              float* losses, float* out, int32_t* loss_flags, void* scratch,
+                              int32_t* status, void* stream);
 
 /* ---- GNN hypernetwork, inference mode ---------------------------------------------------------
  * GNNHypernetwork3 + decoder + fc of DLASSO_GNNHyp3_Progressive (gnn_dlasso_models_progressive.py

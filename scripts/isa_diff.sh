@@ -21,6 +21,9 @@ units() {   # "name source extra-flag" per compile unit of the tree $1
     if grep -q DADMM_ROLES_EVAL "$1/$SUB/dadmm_fused_roles.hip"; then   # the evaluation kernels' build
         echo "dadmm_fused_roles_eval $1/$SUB/dadmm_fused_roles.hip -DDADMM_ROLES_EVAL=1"
     fi
+    if grep -q DADMM_STREAM_EVAL "$1/$SUB/dadmm_stream.hip"; then   # the streamed evaluation kernels' build
+        echo "dadmm_stream_eval $1/$SUB/dadmm_stream.hip -DDADMM_STREAM_EVAL=1"
+    fi
 }
 mkdir "$TMP/a" "$TMP/b"
 { units "$TMP/old" | sed "s|^|$TMP/a |"; units "$ROOT" | sed "s|^|$TMP/b |"; } |
@@ -49,6 +52,9 @@ kstats() {
 }
 rc=0
 for n in $(units "$ROOT" | cut -d' ' -f1); do
+    if ! units "$TMP/old" | cut -d' ' -f1 | grep -qx "$n" && [ -f "$TMP/b/$n.s" ]; then
+        echo "$n: new unit (not in $REV)"; kstats "$TMP/b/$n.s" | sed 's/^/  /'; continue
+    fi
     if [ ! -f "$TMP/a/$n.s" ] || [ ! -f "$TMP/b/$n.s" ]; then rc=1; echo "$n: not compiled on both sides"; continue; fi
     if d=$(diff <(norm "$TMP/a/$n.s") <(norm "$TMP/b/$n.s")); then echo "$n: identical"
     else
